@@ -124,6 +124,27 @@ def synthetic_control(x, y, v2d, num_steps):
     return np.clip(out, 0.0, 5.0).reshape(-1)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: write every array as <out_dir>/<name>.npy in float64, at most `cap` bytes in all.  The arrays share
+    the cap equally, smallest first: one that fits its share is written whole, a larger one as a fixed sample of it (the
+    same seeded, sorted flat indices for the same sizes), so that two runs -- or two builds -- with the same arguments
+    write files that compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    budget = cap - 4096 * len(arrays)                       # room for the .npy headers
+    for i, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].size, k))):
+        a = arrays[name]
+        keep = min(a.size, budget // (8 * (len(arrays) - i)))
+        if keep < a.size:
+            idx = np.random.default_rng(seed).choice(a.size, keep, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        budget -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------
 # multi-rank plumbing (kept in small functions so that the gloo CPU test drives the same code)
 # ---------------------------------------------------------------------------------------------
@@ -462,7 +483,13 @@ def main():
     ap.add_argument("--cpu-worker", type=str, default="", help=argparse.SUPPRESS)   # internal: one 1-core oracle process
     ap.add_argument("--stub-solver", action="store_true",
                     help="CPU rehearsal of the multi-rank control flow (gloo, no GPU, no library); not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, rank 0, at most "
+                         "64 MB: a fixed seeded sample of larger outputs): state_u and adjoint_p (batch x levels x nodes), "
+                         "descent_d (levels x nodes), device (vertex) order; cost (batch); costs_all_ranks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_worker:                      # child of cpu_baseline_sweep: CPU only, never touches the GPU or the library
         print(json.dumps(cpu_worker(*args.cpu_worker.split(","))), flush=True)
@@ -547,10 +574,11 @@ def main():
         d_rhs = ctx.empty(tl)
         d_uhat = ctx.array(np.tile(to_dev(uhat), B))
         sync = ctx.synchronize
+        last = {}
 
         def one_step():
             prob.forward(d_c, d_u, batch=B)
-            J = prob.cost(d_u, d_uhat, d_c, beta, optim, batch=B)
+            J = last["cost"] = prob.cost(d_u, d_uhat, d_c, beta, optim, batch=B)
             prob.adjoint(d_c, d_u, d_uhat, d_p, optim, batch=B)
             prob.descent_direction(d_c, d_u, d_p, beta, d_d, scratch=d_rhs)   # batch member 0 (one control)
             return ranks.gather_costs(J[0])
@@ -564,6 +592,12 @@ def main():
     ranks.fence(sync)
     elapsed = ranks.max_elapsed(time.perf_counter() - t0)
     value = 2 * Nt * B * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:       # before anything below runs the sweep again on these arrays
+        outs = {"costs_all_ranks": np.array(Js)}
+        if not args.stub_solver:
+            outs.update(state_u=d_u.download().reshape(B, Nt + 1, n), adjoint_p=d_p.download().reshape(B, Nt + 1, n),
+                        descent_d=d_d.download().reshape(Nt + 1, n), cost=last["cost"])
+        dump_outputs(args.dump_outputs, outs)
 
     result = {
         "metric": "FCT timesteps/sec (fwd+adj)", "value": value, "unit": "timesteps/s",

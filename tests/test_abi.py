@@ -4,6 +4,8 @@ import ctypes
 import importlib
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -37,8 +39,12 @@ def test_python_binding_covers_header():
 
 
 def test_create_fails_loudly_without_gpu():
-    import torch
-    if torch.cuda.is_available():
+    # asked in a child process: torch brings its own HIP and HSA runtimes, and starting them in this process beside the
+    # ones the library has loaded leaves every later femfct_create here without a usable device
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"],
+                           capture_output=True, text=True, timeout=300)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.split()[-1] == "1":
         pytest.skip("GPU present")
     pkg = importlib.import_module("fem-fct-pdeco_amd")
     with pytest.raises(pkg.FemFctError):
