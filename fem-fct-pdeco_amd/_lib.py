@@ -127,6 +127,9 @@ SIGNATURES = {
     "femfct_schnak_forward_tw": (C.c_int, [_p, _p, _p, _p, _p, _p, _i, _d, _p, _d, _i]),
     "femfct_schnak_adjoint_tw": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _p, _i, _i]),
     "femfct_chtxs_forward": (C.c_int, [_p, _p, _p, _p, _i, _d, _p, _d, _i]),
+    "femfct_nonlinear_forward_ct": (C.c_int, [_p, _p, _p, _i, _p, _i, _d, _d, _i]),
+    "femfct_schnak_forward_ct": (C.c_int, [_p, _p, _p, _p, _i, _p, _p, _i, _d, _p, _d, _i]),
+    "femfct_chtxs_forward_ct": (C.c_int, [_p, _p, _i, _p, _p, _i, _d, _p, _d, _i]),
     "femfct_chtxs_adjoint": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _p, _d, _i, _i]),
     "femfct_traj_krylov_info": (C.c_int, [_p, C.POINTER(StepInfo), _i, _i]),
     "femfct_l2_norm_sq_Q": (C.c_int, [_p, _p, _p, _i, _d, _p, _i]),

@@ -68,6 +68,26 @@ struct Lv {  // VecRef factory bound to the ctx level counter (and to the step o
 
 #define KEY(...) femfct_ctx::GraphKey { __VA_ARGS__ }
 
+// The control a forward sweep of the three systems reads.  Frozen (the reference's helpers.py quirk, helpers.py:577-578,
+// 950-951, 1332-1333): one level, n doubles per batch member, for every step.  Per step (the *_ct entry points, as in the
+// all-time scripts, e.g. Schnak_FCT_PDECO_alltime.py:182-191): a trajectory of num_steps+1 levels per member, and the step
+// from level n to n+1 reads level n+1.  Graph keys: the per-step steps carry their own tag (kind + 100) and c_shared, so
+// they never meet a frozen key; the sweep kind (budgets, kind_fullrows, ...) is shared with the frozen call, the operators
+// being the same.
+struct Ctl {
+    const double* base;
+    bool per_step;
+    int32_t shared;      // per step only: one trajectory for the whole batch
+    static Ctl frozen(const double* c_level) { return Ctl{c_level, false, 0}; }
+    static Ctl traj(const double* c_traj, int32_t c_shared) { return Ctl{c_traj, true, c_shared ? 1 : 0}; }
+    // reference + batch stride of the control the step being enqueued reads
+    VecRef ref(const Lv& L) const { return per_step ? L(base, 1) : make_ref(base); }
+    int64_t bs(int64_t n, int64_t ts) const { return per_step ? (shared ? 0 : ts) : n; }
+    // graph-key tag of a sweep kind, and the key words that follow the frozen key
+    uint64_t tag(int kind) const { return (uint64_t)(per_step ? kind + 100 : kind); }
+    void key_tail(femfct_ctx::GraphKey& k) const { if (per_step) { k.push_back(key_bits((int32_t)1)); k.push_back(key_bits(shared)); } }
+};
+
 int check_common(femfct_ctx* ctx, int32_t num_steps, double dt, int32_t batch) {
     ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
     ARG_TRY(ctx, num_steps >= 1 && dt > 0 && batch >= 1, "need num_steps >= 1, dt > 0, batch >= 1");
@@ -169,31 +189,42 @@ int femfct_bicgstab(femfct_ctx* ctx, const double* mat_ell, int32_t mat_shared, 
 
 // ------------------------------------------------------------------ nonlinear equation
 // du/dt + div(-eps grad u + w u) - u + u^3/3 = c      helpers.py:881-966
-// Aw_ell = assemble_sparse(dot(wind, grad(v))*u*dx); c_level = the control level the reference
-// freezes for the whole sweep (level 1: helpers.py:950-951) as n doubles per batch member.
-int femfct_nonlinear_forward(femfct_ctx* ctx, const double* Aw_ell, const double* c_level, double* u_traj,
-                             int32_t num_steps, double dt, double eps, int32_t batch) {
-    FEMFCT_ENTER(ctx);
+// Aw_ell = assemble_sparse(dot(wind, grad(v))*u*dx); the control: see Ctl.
+static int nonlinear_forward(femfct_ctx* ctx, const double* Aw_ell, Ctl c, double* u_traj, int32_t num_steps, double dt,
+                             double eps, int32_t batch) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
-    ARG_TRY(ctx, Aw_ell && c_level && u_traj, "null argument");
+    ARG_TRY(ctx, Aw_ell && c.base && u_traj, "null argument");
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     const int64_t n = ctx->n, wn = (int64_t)ctx->W * n, ts = (int64_t)(num_steps + 1) * n;
     Lv L{ctx, ctx->d_level, n};
-    auto begin = [&]() {
-        // FCT_alg_ref(-Mat_var1, ...): A = eps*Ad - Aw (helpers.py:935,957); rhs = assemble(c*v*dx) (:956)
-        for (int32_t b = 0; b < batch; ++b) femfct_enqueue_axpby(ctx, wn, eps, ctx->d_Ad, -1.0, Aw_ell, ctx->d_trA + b * wn);
+    // rhs = assemble(c*v*dx) (helpers.py:956)
+    auto load = [&]() {
         LoadSpec ls;
-        ls.s1 = 1.0; ls.k1 = 1.0; ls.p1 = make_ref(c_level); ls.p1_bs = n;
-        return femfct_enqueue_load(ctx, ls, ctx->d_trRhs, batch);
+        ls.s1 = 1.0; ls.k1 = 1.0; ls.p1 = c.ref(L); ls.p1_bs = c.bs(n, ts);
+        return ls;
+    };
+    auto begin = [&]() {
+        // FCT_alg_ref(-Mat_var1, ...): A = eps*Ad - Aw (helpers.py:935,957)
+        for (int32_t b = 0; b < batch; ++b) femfct_enqueue_axpby(ctx, wn, eps, ctx->d_Ad, -1.0, Aw_ell, ctx->d_trA + b * wn);
+        return c.per_step ? (int)FEMFCT_OK : femfct_enqueue_load(ctx, load(), ctx->d_trRhs, batch);
     };
     auto step = [&](int budget, int, int reps) {
-        auto key = KEY((uint64_t)10, key_bits(Aw_ell), key_bits(c_level), key_bits(u_traj), key_bits(num_steps),
+        auto key = KEY(c.tag(10), key_bits(Aw_ell), key_bits(c.base), key_bits(u_traj), key_bits(num_steps),
                        key_bits(dt), key_bits(eps), key_bits(batch), key_bits((int32_t)budget), key_bits(ctx->rel_tol));
+        c.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
             WMassSpec ws;  // Mat_rhs = -M + M_u2/3 (helpers.py:953-955)
             ws.alpha = -1.0; ws.beta = 1.0 / 3.0; ws.f1 = L(u_traj, 0); ws.f2 = L(u_traj, 0); ws.f1_bs = ws.f2_bs = ts;
-            femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trN, batch);
+            if (c.per_step) {       // the step's load c_{n+1}*v*dx rides in the weighted mass's launch: no extra launch
+                FormGroup fg(ctx);
+                fg.weighted_mass(ws, ctx->d_trN, batch);
+                fg.load(load(), ctx->d_trRhs, batch);
+                int r = fg.launch();
+                if (r != FEMFCT_OK) return r;
+            } else {
+                femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trN, batch);
+            }
             femfct_request_fused_end(ctx, 1, false);
             int r = femfct_enqueue_step_ref(ctx, ctx->d_trA, ctx->d_trN, 0, make_ref(ctx->d_trRhs), n, L(u_traj, 0), ts,
                                             dt, L(u_traj, 1), ts, batch, budget);
@@ -203,6 +234,20 @@ int femfct_nonlinear_forward(femfct_ctx* ctx, const double* Aw_ell, const double
     };
     ctx->kind_fullrows.insert(10);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
     return femfct_run_sweep(ctx, 10, num_steps, batch, 0, false, begin, step);
+}
+
+// c_level = the control level the reference freezes for the whole sweep (level 1: helpers.py:950-951), n doubles per member
+int femfct_nonlinear_forward(femfct_ctx* ctx, const double* Aw_ell, const double* c_level, double* u_traj,
+                             int32_t num_steps, double dt, double eps, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return nonlinear_forward(ctx, Aw_ell, Ctl::frozen(c_level), u_traj, num_steps, dt, eps, batch);
+}
+
+// the step to level n+1 reads c_traj level n+1 (nonlinear_FCT_PDECO_alltime.py:189-192)
+int femfct_nonlinear_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const double* c_traj, int32_t c_shared,
+                                double* u_traj, int32_t num_steps, double dt, double eps, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return nonlinear_forward(ctx, Aw_ell, Ctl::traj(c_traj, c_shared), u_traj, num_steps, dt, eps, batch);
 }
 
 // helpers.py:968-1038: p(T) = uhat_T - u(T); FCT_alg_ref(-Mat_p, 0, p_{n+1}, non_flux_mat = M_u2(u_n) - M)
@@ -246,6 +291,9 @@ int femfct_schnak_forward(femfct_ctx* ctx, const double* Aw_ell, const double* c
     return femfct_schnak_forward_tw(ctx, Aw_ell, nullptr, c_level, u_traj, v_traj, num_steps, dt, par, rescaling, batch);
 }
 
+static int schnak_forward(femfct_ctx* ctx, const double* Aw_ell, const double* wind_scale_host, Ctl c, double* u_traj,
+                          double* v_traj, int32_t num_steps, double dt, const double* par, double rescaling, int32_t batch);
+
 // The same with a separable time-dependent wind w(x, t) = s(t) w0(x) (Schnak_FCT_PDECO_alltime.py:55,174-175:
 // sin(2 pi t) * rotation, re-assembled every step; helpers.py:566 sets wind.t = t_{n+1} before assembling):
 // Aw_ell = assemble(dot(w0, grad(v))*u*dx), wind_scale_host[k] = s(t_k), k = 0..num_steps; the step to level n+1
@@ -254,9 +302,25 @@ int femfct_schnak_forward_tw(femfct_ctx* ctx, const double* Aw_ell, const double
                              double* u_traj, double* v_traj, int32_t num_steps, double dt, const double* par,
                              double rescaling, int32_t batch) {
     FEMFCT_ENTER(ctx);
+    return schnak_forward(ctx, Aw_ell, wind_scale_host, Ctl::frozen(c_level), u_traj, v_traj, num_steps, dt, par, rescaling,
+                          batch);
+}
+
+// per-step control (Schnak_FCT_PDECO_alltime.py:182-191): the step to level n+1 reads c_traj level n+1; wind_scale_host
+// as in femfct_schnak_forward_tw (NULL: stationary wind)
+int femfct_schnak_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const double* wind_scale_host, const double* c_traj,
+                             int32_t c_shared, double* u_traj, double* v_traj, int32_t num_steps, double dt,
+                             const double* par, double rescaling, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return schnak_forward(ctx, Aw_ell, wind_scale_host, Ctl::traj(c_traj, c_shared), u_traj, v_traj, num_steps, dt, par,
+                          rescaling, batch);
+}
+
+static int schnak_forward(femfct_ctx* ctx, const double* Aw_ell, const double* wind_scale_host, Ctl c, double* u_traj,
+                          double* v_traj, int32_t num_steps, double dt, const double* par, double rescaling, int32_t batch) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
-    ARG_TRY(ctx, Aw_ell && c_level && u_traj && v_traj && par && rescaling != 0.0, "bad argument");
+    ARG_TRY(ctx, Aw_ell && c.base && u_traj && v_traj && par && rescaling != 0.0, "bad argument");
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_krylov_ws(ctx, batch)) != FEMFCT_OK) return rc;
     const double Du = par[0], Dv = par[1], c_b = par[2], gam = par[3], om1 = par[4], om2 = par[5];
@@ -284,15 +348,16 @@ int femfct_schnak_forward_tw(femfct_ctx* ctx, const double* Aw_ell, const double
         return wsc ? (int)FEMFCT_OK : wind_ops(0);
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY((uint64_t)12, key_bits(Aw_ell), key_bits(c_level), key_bits(u_traj), key_bits(v_traj),
+        auto key = KEY(c.tag(12), key_bits(Aw_ell), key_bits(c.base), key_bits(u_traj), key_bits(v_traj),
                        key_bits(num_steps), key_bits(dt), key_bits(Du), key_bits(Dv), key_bits(c_b), key_bits(gam),
                        key_bits(om1), key_bits(om2), key_bits(rescaling), key_bits(batch), key_bits((int32_t)budget),
                        key_bits((int32_t)kbudget), key_bits(ctx->rel_tol), key_bits(ctx->kry_tol),
                        key_bits((int32_t)femfct_species_cheb(ctx, 12)), key_bits(wsc));
+        c.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
             if (wsc) wind_ops(1);       // wind.t = t_{n+1} (helpers.py:565-566)
             LoadSpec l1;  // (gamma/r*c + gamma*u_n^2*v_n)*v*dx  (helpers.py:584-585)
-            l1.s1 = 1.0; l1.k1 = gam / rescaling; l1.p1 = make_ref(c_level); l1.p1_bs = n;
+            l1.s1 = 1.0; l1.k1 = gam / rescaling; l1.p1 = c.ref(L); l1.p1_bs = c.bs(n, ts);
             l1.k2 = gam; l1.q1 = L(u_traj, 0); l1.q2 = L(u_traj, 0); l1.q3 = L(v_traj, 0);
             l1.q1_bs = l1.q2_bs = l1.q3_bs = ts;
             LoadSpec l2;  // M@v_n + dt*assemble(gamma*c_b*v*dx)  (helpers.py:594,596): level n only, so it rides in l1's launch
@@ -416,13 +481,12 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
 }
 
 // ------------------------------------------------------------------ chemotaxis
-// helpers.py:1250-1385.  par = {delta, Dm, Df, chi, eta}
-int femfct_chtxs_forward(femfct_ctx* ctx, const double* c_level, double* u_traj, double* v_traj, int32_t num_steps,
-                         double dt, const double* par, double rescaling, int32_t batch) {
-    FEMFCT_ENTER(ctx);
+// helpers.py:1250-1385.  par = {delta, Dm, Df, chi, eta}; the control: see Ctl
+static int chtxs_forward(femfct_ctx* ctx, Ctl c, double* u_traj, double* v_traj, int32_t num_steps, double dt,
+                         const double* par, double rescaling, int32_t batch) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
-    ARG_TRY(ctx, c_level && u_traj && v_traj && par && rescaling != 0.0, "bad argument");
+    ARG_TRY(ctx, c.base && u_traj && v_traj && par && rescaling != 0.0, "bad argument");
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_krylov_ws(ctx, batch)) != FEMFCT_OK) return rc;
     const double delta = par[0], Dm = par[1], Df = par[2], chi = par[3], eta = par[4];
@@ -434,15 +498,16 @@ int femfct_chtxs_forward(femfct_ctx* ctx, const double* c_level, double* u_traj,
         return femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trBase, 1);
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY((uint64_t)14, key_bits(c_level), key_bits(u_traj), key_bits(v_traj), key_bits(num_steps),
+        auto key = KEY(c.tag(14), key_bits(c.base), key_bits(u_traj), key_bits(v_traj), key_bits(num_steps),
                        key_bits(dt), key_bits(delta), key_bits(Dm), key_bits(Df), key_bits(chi), key_bits(eta),
                        key_bits(rescaling), key_bits(batch), key_bits((int32_t)budget), key_bits((int32_t)kbudget),
                        key_bits(ctx->rel_tol), key_bits(ctx->kry_tol),
                        key_bits((int32_t)femfct_species_cheb(ctx, 14)));
+        c.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
             LoadSpec l2;  // assemble(v_n*v*dx + dt*c*u_n/r*v*dx)  (helpers.py:1339-1340)
             l2.s0 = 1.0; l2.mx = L(v_traj, 0); l2.mx_bs = ts; l2.s1 = dt / rescaling; l2.k2 = 1.0;
-            l2.q1 = make_ref(c_level); l2.q1_bs = n; l2.q2 = L(u_traj, 0); l2.q2_bs = ts;
+            l2.q1 = c.ref(L); l2.q1_bs = c.bs(n, ts); l2.q2 = L(u_traj, 0); l2.q2_bs = ts;
             femfct_enqueue_load(ctx, l2, ctx->d_trRhs2, batch);
             int r = femfct_enqueue_species_solve(ctx, 14, ctx->d_trBase, 1, ctx->d_trRhs2, L(v_traj, 0), ts, L(v_traj, 1), ts, batch, kbudget, dt * Df);
             if (r != FEMFCT_OK) return r;
@@ -457,6 +522,20 @@ int femfct_chtxs_forward(femfct_ctx* ctx, const double* c_level, double* u_traj,
     };
     ctx->kind_fullrows.insert(14);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
     return femfct_run_sweep(ctx, 14, num_steps, batch, 0, true, begin, step);
+}
+
+// c_level: the frozen control level (helpers.py:1332-1333), n doubles per batch member
+int femfct_chtxs_forward(femfct_ctx* ctx, const double* c_level, double* u_traj, double* v_traj, int32_t num_steps,
+                         double dt, const double* par, double rescaling, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return chtxs_forward(ctx, Ctl::frozen(c_level), u_traj, v_traj, num_steps, dt, par, rescaling, batch);
+}
+
+// per-step control (chemotaxis_mimura_FCT_PGD_alltime.py:180-183: f_rhs = f_n + dt*c_{n+1}*m_n)
+int femfct_chtxs_forward_ct(femfct_ctx* ctx, const double* c_traj, int32_t c_shared, double* u_traj, double* v_traj,
+                            int32_t num_steps, double dt, const double* par, double rescaling, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return chtxs_forward(ctx, Ctl::traj(c_traj, c_shared), u_traj, v_traj, num_steps, dt, par, rescaling, batch);
 }
 
 // helpers.py:1387-1581.  alltime = 0: optim == "finaltime" (uhat/vhat: n doubles per member, terminal

@@ -397,6 +397,11 @@ class Context:
         check(self.handle, lib.femfct_nonlinear_forward(self.handle, dptr(Aw), dptr(c_level), dptr(u), int(num_steps),
                                                         float(dt), float(eps), int(batch)))
 
+    def nonlinear_forward_ct(self, Aw, c_traj, u, num_steps, dt, eps, batch=1, c_shared=False):
+        """Per-step control: the step to level n+1 reads level n+1 of c_traj ((num_steps+1)*n per member)."""
+        check(self.handle, lib.femfct_nonlinear_forward_ct(self.handle, dptr(Aw), dptr(c_traj), int(bool(c_shared)), dptr(u),
+                                                           int(num_steps), float(dt), float(eps), int(batch)))
+
     def nonlinear_adjoint(self, Aw, u, uhat_T, p, num_steps, dt, eps, batch=1):
         check(self.handle, lib.femfct_nonlinear_adjoint(self.handle, dptr(Aw), dptr(u), dptr(uhat_T), dptr(p),
                                                         int(num_steps), float(dt), float(eps), int(batch)))
@@ -408,6 +413,15 @@ class Context:
         check(self.handle, lib.femfct_schnak_forward_tw(self.handle, dptr(Aw), None if ws is None else _host_ptr(ws),
                                                         dptr(c_level), dptr(u), dptr(v), int(num_steps), float(dt),
                                                         _host_ptr(par), float(rescaling), int(batch)))
+
+    def schnak_forward_ct(self, Aw, c_traj, u, v, num_steps, dt, par, rescaling=1.0, batch=1, wind_scale=None,
+                          c_shared=False):
+        """schnak_forward with a per-step control: the step to level n+1 reads level n+1 of c_traj."""
+        par = _as_f64(par)
+        ws = None if wind_scale is None else _wind_scale(wind_scale, num_steps)
+        check(self.handle, lib.femfct_schnak_forward_ct(self.handle, dptr(Aw), None if ws is None else _host_ptr(ws),
+                                                        dptr(c_traj), int(bool(c_shared)), dptr(u), dptr(v), int(num_steps),
+                                                        float(dt), _host_ptr(par), float(rescaling), int(batch)))
 
     def schnak_adjoint(self, AwT, u, v, uhat_T, vhat_T, p, q, num_steps, dt, par, batch=1, alltime=False, wind_scale=None):
         par = _as_f64(par)
@@ -421,6 +435,13 @@ class Context:
         par = _as_f64(par)
         check(self.handle, lib.femfct_chtxs_forward(self.handle, dptr(c_level), dptr(u), dptr(v), int(num_steps),
                                                     float(dt), _host_ptr(par), float(rescaling), int(batch)))
+
+    def chtxs_forward_ct(self, c_traj, u, v, num_steps, dt, par, rescaling=0.1, batch=1, c_shared=False):
+        """chtxs_forward with a per-step control: the step to level n+1 reads level n+1 of c_traj."""
+        par = _as_f64(par)
+        check(self.handle, lib.femfct_chtxs_forward_ct(self.handle, dptr(c_traj), int(bool(c_shared)), dptr(u), dptr(v),
+                                                       int(num_steps), float(dt), _host_ptr(par), float(rescaling),
+                                                       int(batch)))
 
     def chtxs_adjoint(self, u, v, uhat, vhat, p, q, c, num_steps, dt, par, rescaling=0.1, alltime=True, batch=1):
         par = _as_f64(par)

@@ -10,6 +10,9 @@ adjoints, controls and targets stay in HBM and only scalars (costs, norms) reach
 ``speculative=True`` evaluates all Armijo trial steps s0/2^k of an iteration as one batch of
 independent trajectories (helpers.py:1681-1708 picks the first accepted k: same iterate, the states
 agree to the solver tolerance) -- the lever that fills the GPU on these small meshes.
+``control_per_step=True`` steps the state with the control of the level being computed (the step to
+level n+1 reads level n+1), as the reference's all-time scripts do; by default the state solvers
+freeze the control at level 1 like helpers.py (see systems.py).
 """
 from __future__ import annotations
 
@@ -44,14 +47,17 @@ class SystemPDECO:
     FunctionSpace); host vectors are in FEniCS DoF order like the reference's."""
 
     def __init__(self, problem: str, V: SquareMeshP1, num_steps: int, dt: float, device_id: int = 0, wind=None,
-                 wind_scale=None, **overrides):
+                 wind_scale=None, control_per_step=False, **overrides):
         """``wind`` / ``wind_scale`` (problem "schnak" only): the separable time-dependent wind ``s(t) w0(x)`` of the
-        script BASELINE config 3 names (Schnak_FCT_PDECO_alltime.py:55,174-175), see systems.solve_schnak_system."""
+        script BASELINE config 3 names (Schnak_FCT_PDECO_alltime.py:55,174-175), see systems.solve_schnak_system.
+        ``control_per_step``: the state step to level n+1 reads control level n+1 (the all-time scripts, e.g.
+        Schnak_FCT_PDECO_alltime.py:182-191) instead of level 1 for every step (helpers.py:577-578 etc.)."""
         if problem not in DEFAULTS:
             raise ValueError(f"unknown problem '{problem}' (one of {sorted(DEFAULTS)})")
         if (wind is not None or wind_scale is not None) and problem != "schnak":
             raise ValueError("wind / wind_scale: only the Schnakenberg driver has a time-dependent wind")
         self.problem, self.V, self.Nt, self.dt = problem, V, int(num_steps), float(dt)
+        self.per_step = bool(control_per_step)
         self.P = dict(DEFAULTS[problem])
         unknown = set(overrides) - set(self.P)
         if unknown:
@@ -115,8 +121,18 @@ class SystemPDECO:
 
     # ------------------------------------------------------------------ solves (batch of B trajectories)
     def _state(self, c, u, v, clev, B):
-        """solve_<problem>(c, u, v): the control is frozen at time level 1 (helpers.py:577-578 etc.)"""
+        """solve_<problem>(c, u, v): the control is frozen at time level 1 (helpers.py:577-578 etc.), or with
+        ``control_per_step`` the B control trajectories (stride tl) are read level by level (clev unused)"""
         n, tl = self.n, self.tl
+        if self.per_step:
+            if self.problem == "nonlinear":
+                self.ctx.nonlinear_forward_ct(self.Aw, c, u, self.Nt, self.dt, self.eps, batch=B)
+            elif self.problem == "schnak":
+                self.ctx.schnak_forward_ct(self.Aw, c, u, v, self.Nt, self.dt, self.par, 1.0, batch=B,
+                                           wind_scale=self.wscale)
+            else:
+                self.ctx.chtxs_forward_ct(c, u, v, self.Nt, self.dt, self.par, 0.1, batch=B)
+            return
         for b in range(B):
             clev.copy_from(c, n, dst_off=b * n, src_off=b * tl + n)
         if self.problem == "nonlinear":
@@ -185,7 +201,7 @@ class SystemPDECO:
         q = self._zeros(tl) if self.two else None
         c, d, cbak = self._zeros(tl), self._zeros(tl), self._zeros(tl)
         tg = [self._up(t) for t in targets]
-        clev = self._zeros(B * n)
+        clev = None if self.per_step else self._zeros(B * n)
         uB = traj0(ic[0], B)
         vB = traj0(ic[1], B) if self.two else None
         cB = self._zeros(B * tl)
@@ -291,7 +307,8 @@ class SystemPDECO:
 
 
 def projected_gradient_descent(problem, V, ic, targets, num_steps, dt, speculative=True, device_id=0, wind=None,
-                               wind_scale=None, **overrides):
+                               wind_scale=None, control_per_step=False, **overrides):
     """One call = one run of the refactored driver ``problem`` (see module docstring)."""
-    with SystemPDECO(problem, V, num_steps, dt, device_id=device_id, wind=wind, wind_scale=wind_scale, **overrides) as prob:
+    with SystemPDECO(problem, V, num_steps, dt, device_id=device_id, wind=wind, wind_scale=wind_scale,
+                     control_per_step=control_per_step, **overrides) as prob:
         return prob.run(ic, targets, speculative=speculative)

@@ -8,8 +8,12 @@ in-place mutation behaviour), running as device-resident sweeps through the C AB
 
 ``V`` is the ``SquareMeshP1`` descriptor (stand-in for the dolfin FunctionSpace); a ``control_fun``
 is a Python float (the reference passes a constant dolfin Expression for target generation).
-Reference quirks are reproduced: the forward solvers freeze the control at time
-level 1 (helpers.py:577-578, 950-951, 1332-1333) and zero ``var[nodes:]`` in place first.
+Reference quirks are reproduced by default: the forward solvers freeze the control at
+time level 1 (helpers.py:577-578, 950-951, 1332-1333) and zero ``var[nodes:]`` in place first.
+``control_per_step=True`` (keyword-only) steps with the control of the level being computed instead, as
+the reference's all-time scripts do (e.g. Schnak_FCT_PDECO_alltime.py:182-191): the step from level n to
+n+1 reads ``control[(n+1)*nodes:(n+2)*nodes]``; level 0 is never read.  With a ``control_fun`` the two
+modes are the same.
 """
 from __future__ import annotations
 
@@ -145,6 +149,19 @@ def _frozen_control(control, control_fun, nodes):
     return np.array(control[nodes:2 * nodes], dtype=np.float64)   # level 1 for every step
 
 
+def _step_control(control, control_fun, nodes, num_steps, control_per_step):
+    """The control a forward sweep reads, as (host array, per_step): the frozen level 1 (n values), or with
+    ``control_per_step`` and no ``control_fun`` the whole trajectory ((num_steps+1)*nodes values, checked here, before
+    any device work or in-place mutation)."""
+    if not control_per_step or control_fun is not None:
+        return _frozen_control(control, control_fun, nodes), False
+    c = np.asarray(control, dtype=np.float64).ravel()
+    if c.size != (num_steps + 1) * nodes:
+        raise ValueError(f"control_per_step: control has {c.size} values, expected (num_steps + 1) * nodes = "
+                         f"{(num_steps + 1) * nodes}")
+    return c, True
+
+
 class _Bufs:
     """Host (FEniCS DoF order, level-major) <-> device (vertex order) staging of one call."""
 
@@ -176,10 +193,12 @@ class _Bufs:
 
 # ----------------------------------------------------------------------------- nonlinear
 def solve_nonlinear_equation(control, var1, var2, V, nodes, num_steps, dt, dof_neighbors,
-                             control_fun=None, show_plots=False, vertex_to_dof=None):
-    """helpers.py:881-966: mutates ``var1[nodes:]`` in place, returns ``(var1, None)``."""
+                             control_fun=None, show_plots=False, vertex_to_dof=None, *, control_per_step=False):
+    """helpers.py:881-966: mutates ``var1[nodes:]`` in place, returns ``(var1, None)``.
+    ``control_per_step``: see the module docstring (nonlinear_FCT_PDECO_alltime.py:189-192)."""
     if var2 is not None:
         warnings.warn("Warning: 'var2' is not None. Ensure this is intentional.")
+    c, per_step = _step_control(control, control_fun, nodes, num_steps, control_per_step)
     S = _system(V)
     eps, _, wind = get_nonlinear_eqns_params()
     Aw, _ = S.convection(wind, "nonlinear")
@@ -187,7 +206,10 @@ def solve_nonlinear_equation(control, var1, var2, V, nodes, num_steps, dt, dof_n
     B = _Bufs(S)
     try:
         u = B.up(var1)
-        S.ctx.nonlinear_forward(Aw, B.up(_frozen_control(control, control_fun, nodes)), u, num_steps, dt, eps)
+        if per_step:
+            S.ctx.nonlinear_forward_ct(Aw, B.up(c), u, num_steps, dt, eps)
+        else:
+            S.ctx.nonlinear_forward(Aw, B.up(c), u, num_steps, dt, eps)
         B.down(u, var1)
     finally:
         B.free()
@@ -245,14 +267,16 @@ def _wind_factors(wind_scale, num_steps, dt, t0=0.0, T=None):
 
 
 def solve_schnak_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbors,
-                        control_fun=None, rescaling=1, wind=None, wind_scale=None):
+                        control_fun=None, rescaling=1, wind=None, wind_scale=None, *, control_per_step=False):
     """helpers.py:511-597: mutates and returns ``(var1, var2)``.
 
     Extension for the script BASELINE config 3 names (Schnak_FCT_PDECO_alltime.py:55,174-175: the wind
     ``(-(y-.5), (x-.5)) * sin(2 pi t)``, re-assembled per step): ``wind=w0`` (a function ``(x, y) -> (wx, wy)``,
     default the stationary wind of helpers.py:506-508) and ``wind_scale=s`` (callable ``s(t)`` or the array
     ``s(t_0..t_Nt)``) give the separable wind ``s(t) w0(x)``; the step to level n+1 uses ``s(t_{n+1})``
-    (helpers.py:565-566: ``t += dt; wind.t = t``)."""
+    (helpers.py:565-566: ``t += dt; wind.t = t``).
+    ``control_per_step``: see the module docstring (Schnak_FCT_PDECO_alltime.py:182-191)."""
+    c, per_step = _step_control(control, control_fun, nodes, num_steps, control_per_step)
     S = _system(V)
     par, wind0 = _schnak_par()
     Aw, _ = S.convection(wind or wind0, None if wind is not None else "schnak")
@@ -261,8 +285,8 @@ def solve_schnak_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighb
     B = _Bufs(S)
     try:
         u, v = B.up(var1), B.up(var2)
-        S.ctx.schnak_forward(Aw, B.up(_frozen_control(control, control_fun, nodes)), u, v, num_steps, dt, par, rescaling,
-                             wind_scale=_wind_factors(wind_scale, num_steps, dt))
+        fwd = S.ctx.schnak_forward_ct if per_step else S.ctx.schnak_forward
+        fwd(Aw, B.up(c), u, v, num_steps, dt, par, rescaling, wind_scale=_wind_factors(wind_scale, num_steps, dt))
         B.down(u, var1)
         B.down(v, var2)
     finally:
@@ -302,8 +326,11 @@ def _chtxs_par():
 
 def solve_chtxs_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbors,
                        control_fun=None, show_plots=False, vertex_to_dof=None,
-                       generation_mode=False, output_dir=None, rescaling=1 / 10):
-    """helpers.py:1250-1385."""
+                       generation_mode=False, output_dir=None, rescaling=1 / 10, *, control_per_step=False):
+    """helpers.py:1250-1385.  ``control_per_step``: see the module docstring
+    (chemotaxis_mimura_FCT_PGD_alltime.py:180-183; generation mode takes one control level and ignores it)."""
+    if not generation_mode:
+        c, per_step = _step_control(control, control_fun, nodes, num_steps, control_per_step)
     S = _system(V)
     par = _chtxs_par()
     B = _Bufs(S)
@@ -330,7 +357,10 @@ def solve_chtxs_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbo
         var1[nodes:] = np.zeros(num_steps * nodes)
         var2[nodes:] = np.zeros(num_steps * nodes)
         u, v = B.up(var1), B.up(var2)
-        S.ctx.chtxs_forward(B.up(_frozen_control(control, control_fun, nodes)), u, v, num_steps, dt, par, rescaling)
+        if per_step:
+            S.ctx.chtxs_forward_ct(B.up(c), u, v, num_steps, dt, par, rescaling)
+        else:
+            S.ctx.chtxs_forward(B.up(c), u, v, num_steps, dt, par, rescaling)
         B.down(u, var1)
         B.down(v, var2)
     finally:

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH; 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
+#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
 
 typedef struct femfct_ctx femfct_ctx;
 
@@ -337,6 +337,19 @@ int femfct_chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
                          const double* vhat, double* p_traj, double* q_traj, const double* c_traj,
                          int32_t num_steps, double dt, const double* par, double rescaling, int32_t alltime,
                          int32_t batch);
+/* The three forward sweeps with a per-step control, as in the reference's all-time scripts
+ * (nonlinear_FCT_PDECO_alltime.py:189-192, Schnak_FCT_PDECO_alltime.py:182-191,
+ * chemotaxis_mimura_FCT_PGD_alltime.py:180-183): the step from level n to level n+1 reads level n+1 of c_traj
+ * (level 0 is never read).  c_traj: (num_steps+1)*n doubles per batch member, batch stride (num_steps+1)*n;
+ * c_shared != 0: one trajectory for the whole batch (as femfct_solidbody_forward).  Everything else as the frozen-level
+ * calls above; femfct_schnak_forward_ct takes wind_scale_host as femfct_schnak_forward_tw (NULL: stationary wind). */
+int femfct_nonlinear_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const double* c_traj, int32_t c_shared,
+                                double* u_traj, int32_t num_steps, double dt, double eps, int32_t batch);
+int femfct_schnak_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const double* wind_scale_host, const double* c_traj,
+                             int32_t c_shared, double* u_traj, double* v_traj, int32_t num_steps, double dt,
+                             const double* par, double rescaling, int32_t batch);
+int femfct_chtxs_forward_ct(femfct_ctx* ctx, const double* c_traj, int32_t c_shared, double* u_traj, double* v_traj,
+                            int32_t num_steps, double dt, const double* par, double rescaling, int32_t batch);
 /* BiCGStab diagnostics of the most recent sweep that used it: info_host[step*batch + b] */
 int femfct_traj_krylov_info(femfct_ctx* ctx, femfct_step_info* info_host, int32_t num_steps, int32_t batch);
 
