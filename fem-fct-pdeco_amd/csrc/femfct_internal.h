@@ -157,6 +157,14 @@ struct femfct_ctx {
     size_t trAall_count = 0;
     bool preassemble = true;
     double preassemble_max_bytes = 16.0 * 1024 * 1024 * 1024;
+    // low-order operators of the pre-assembled sequence, built with it (FEMFCT_PREBUILD_LOW): L_k at d_lowall, D_k at
+    // d_lowall + low_doff, each in the layout of d_trAall.  low_src / low_dt: the sequence and dt they were built from
+    // (null: none valid); the tile step reads them only when its A and dt match.
+    bool prebuild_low = true;
+    double* d_lowall = nullptr;
+    size_t lowall_count = 0, low_doff = 0;
+    const double* low_src = nullptr;
+    double low_dt = 0.0;
     double *d_trA = nullptr, *d_trN = nullptr, *d_trRhs = nullptr;  // per-step operators [B*W*n], [B*n]
     int32_t* d_level = nullptr;                                     // [2]: current level, step ordinal
     StepCtl* d_log = nullptr;                                       // [tr_steps * tr_batch]
@@ -258,7 +266,8 @@ int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double
                                double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch = 0, int defer = 0);
 int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, struct MatRef A, const double* Nm, int32_t nshared,
                                      struct VecRef rhs, int64_t rhs_bstride, struct VecRef u_n, int64_t u_bstride, double dt,
-                                     int32_t batch);
+                                     int32_t batch, bool pre = false);
+int femfct_enqueue_low_seq(femfct_ctx* ctx, const double* A, double* L, double* D, int32_t entries, double dt);
 bool femfct_tile_big(const femfct_ctx* ctx, const TilePlan& pl);   // more workgroups than in-kernel partials
 int femfct_enqueue_tile_cheb(femfct_ctx* ctx, const TilePlan& pl, const double* b, const double* in_mid,
                              const double* in_old, double* y_out, int k_first, int k_last, const double* omegas,
@@ -273,7 +282,7 @@ bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch);
 bool femfct_rotation_is_geometric(femfct_ctx* ctx, const double* Arot, double* om_out);   // kernels_asm.hip
 bool femfct_geom_mass(const femfct_ctx* ctx);   // M may be derived from the cell geometry instead of loaded
 int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const double* in_mid, const double* in_old,
-                                        int k_first, int k_last, const double* omegas, double md_scale, const double* D,
+                                        int k_first, int k_last, const double* omegas, double md_scale, struct MatRef D,
                                         const double* ulow, double dt, struct VecRef out, int64_t out_bstride, int32_t batch,
                                         bool fuse_end);
 int femfct_tile4_init(femfct_ctx* ctx);

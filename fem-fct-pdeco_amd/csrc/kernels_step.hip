@@ -702,6 +702,16 @@ int femfct_enqueue_step_op(femfct_ctx* ctx, MatRef A, const SbOpArgs* sb, const 
                          ? reinterpret_cast<uint8_t*>(ctx->d_Lmask + 1) : nullptr;
     // symmetric storage of D between k_build_low and the 2-D tile limiter (both sides of this step or neither)
     const int half_d = (tile4 && ctx->half_d && ctx->structured && ctx->implicit_cols && W == 7) ? 1 : 0;
+    // L_k and D_k of this very sequence entry were built before the sweep (femfct_prebuild_low): the first Jacobi launch
+    // reads L_k instead of building it and the fused limiter reads D_k -- both only on the path that consumes D there
+    MatRef L_pre = A, D_pre{ctx->d_D, nullptr, 0, 0, (int64_t)W * n};
+    const bool pre_low = fused_build && !N && A.level && A.base == ctx->low_src && dt == ctx->low_dt && ctx->fuse_dudt &&
+                         femfct_cheb_flux_fusable(ctx, batch);
+    if (pre_low) {
+        L_pre.base = ctx->d_lowall;
+        D_pre = A;
+        D_pre.base = ctx->d_lowall + ctx->low_doff;
+    }
     if (sb) {
         femfct_prof_begin(ctx, KC_BUILD_LOW);
         if (sb->rot_geom)
@@ -747,8 +757,11 @@ int femfct_enqueue_step_op(femfct_ctx* ctx, MatRef A, const SbOpArgs* sb, const 
         // residual tests move out of the later launches into that kernel (exact_k = -1; solve_ctl.h: deferred_test_*)
         const bool defer = ctx->defer_check && fused_build && units >= 2 && units <= 4 && exact_k == 0 && ctx->fuse_dudt;
         if (defer) exact_k = -units;
-        if (fused_build)
-            femfct_enqueue_tile_build_jacobi(ctx, tp, A, N, nshared, rhs, rhs_bstride, u_n, u_bstride, dt, batch);
+        if (fused_build) {
+            int r = femfct_enqueue_tile_build_jacobi(ctx, tp, pre_low ? L_pre : A, N, nshared, rhs, rhs_bstride, u_n, u_bstride,
+                                                     dt, batch, pre_low);
+            if (r != FEMFCT_OK) return r;
+        }
         for (int s = fused_build ? 1 : 0; s < units; ++s)
             femfct_enqueue_tile_jacobi(ctx, tp, ctx->d_L, ctx->d_b, ctx->d_xa, ctx->d_xb, s,
                                        fused_build ? tp.tiles * tp.tiles : (int)g.grid.x, batch,
@@ -778,7 +791,7 @@ int femfct_enqueue_step_op(femfct_ctx* ctx, MatRef A, const SbOpArgs* sb, const 
             // iterations tail..20 of du/dt + flux + limiter (+ step end) in one launch
             const bool fuse_end = ctx->end_req_delta != 0 && ctx->d_ticket && ctx->d_level && ctx->d_log && !ctx->prof_on;
             int r = femfct_enqueue_tile_cheb_flux_limit(ctx, ctx->d_rdu, ctx->d_y0, ctx->d_y2, tail, 20, om.data(), 1.25,
-                                                        ctx->d_D, ulow, dt, u_out, out_bstride, batch, fuse_end);
+                                                        D_pre, ulow, dt, u_out, out_bstride, batch, fuse_end);
             if (r != FEMFCT_OK) return r;
             if (fuse_end) ctx->end_fused = true;
             step_done = true;

@@ -500,7 +500,9 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
 // L, D, b): every thread builds the row of its patch node from A (a_ji comes from the neighbour thread
 // through LDS, three slots at a time), the tile's owned rows are stored for the later launches / the
 // limiter, then K Jacobi sweeps run as in k_tile_jacobi.  Saves one dependent launch per time step.
-template <int H>
+// PRE = 1: the operator was built before the sweep (k_low_seq): A_ref is the L_k sequence, read instead of built (no
+// a_ji exchange, no D store: the limiter reads D_k from the sequence); the owned rows of L still go to L_ for launch 1.
+template <int H, int PRE>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, int nshared,
                     VecRef rhs_ref, int64_t rhs_bstride, VecRef u_ref, int64_t u_bstride,
@@ -509,7 +511,7 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
                     StepCtl* __restrict__ ctl_, int K) {
     constexpr int W = 7;
     __shared__ double xs[2][TILE_L * TILE_LD];
-    __shared__ double as[3][TILE_L * TILE_LD];
+    __shared__ double as[PRE ? 1 : 3][TILE_L * TILE_LD];
     __shared__ double smem[96];
     const int bz = blockIdx.z;
     const int wg = blockIdx.y * gridDim.x + blockIdx.x;
@@ -526,67 +528,88 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
     if (rhs) rhs += bz * rhs_bstride;
     const double* u = vec_ptr(u_ref) + bz * u_bstride;
     const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
-    // neighbour s exists in the grid (otherwise the ELL slot is padding: column = row, value 0)
-    const int dx[6] = {1, 1, 0, -1, -1, 0}, dy[6] = {0, 1, 1, 0, -1, -1};
-    bool ex[W - 1];
-#pragma unroll
-    for (int s = 0; s < W - 1; ++s) {
-        const int nx = g.gx + dx[s], ny = g.gy + dy[s];
-        ex[s] = g.inside && nx >= 0 && nx < N && ny >= 0 && ny < N;
-    }
-    double av[W - 1], at[W - 1], a0 = 0.0;
-#pragma unroll
-    for (int s = 0; s < W - 1; ++s) av[s] = 0.0;
-    if (g.inside) {
-        a0 = A[g.i];
-#pragma unroll
-        for (int s = 1; s < W; ++s) av[s - 1] = A[(int64_t)s * n + g.i];
-    }
-    // a_ji of slot s lives in row j at the opposite slot: slots E,NE,N <-> W,SW,S
-#pragma unroll
-    for (int s = 0; s < 3; ++s) as[s][g.self] = av[s + 3];
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 3; ++s) at[s] = as[s][g.nb[s]];
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 3; ++s) as[s][g.self] = av[s];
-    __syncthreads();
-#pragma unroll
-    for (int s = 3; s < 6; ++s) at[s] = as[s - 3][g.nb[s]];
     double lv[W - 1], dv[W - 1], dsum = 0.0, rs = 0.0;
-#pragma unroll
-    for (int s = 0; s < W - 1; ++s) {
-        const double a = av[s];
-        const double d = ex[s] ? fmax(0.0, fmax(a, at[s])) : 0.0;   // d_ij = max(0, a_ij, a_ji)
-        dsum += d;
-        double l = dt * (a - d);
-        if (Nm && g.inside) l += dt * Nm[(int64_t)(s + 1) * n + g.i];
-        lv[s] = l;
-        dv[s] = d;
-        rs += l;
-    }
     double dg = 1.0, rdg = 1.0, bv = 0.0, xi = 0.0;
-    if (g.inside) {
-        const double mli = ml[g.i];
-        double ld = mli + dt * (a0 + dsum);                         // d_ii = -sum_j d_ij
-        if (Nm) ld += dt * Nm[g.i];
-        rs += ld;
-        dg = ld;
-        rdg = 1.0 / dg;
-        xi = u[g.i];
-        bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+    if constexpr (PRE) {
+        // the rows k_low_seq built (bitwise those of the branch below); the row sum in the same order
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) lv[s] = 0.0;
+        if (g.inside) {
+            dg = A[g.i];
+#pragma unroll
+            for (int s = 1; s < W; ++s) lv[s - 1] = A[(int64_t)s * n + g.i];
+        }
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) rs += lv[s];
+        if (g.inside) {
+            const double mli = ml[g.i];
+            rs += dg;
+            rdg = 1.0 / dg;
+            xi = u[g.i];
+            bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+        }
+    } else {
+        // neighbour s exists in the grid (otherwise the ELL slot is padding: column = row, value 0)
+        const int dx[6] = {1, 1, 0, -1, -1, 0}, dy[6] = {0, 1, 1, 0, -1, -1};
+        bool ex[W - 1];
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const int nx = g.gx + dx[s], ny = g.gy + dy[s];
+            ex[s] = g.inside && nx >= 0 && nx < N && ny >= 0 && ny < N;
+        }
+        double av[W - 1], at[W - 1], a0 = 0.0;
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) av[s] = 0.0;
+        if (g.inside) {
+            a0 = A[g.i];
+#pragma unroll
+            for (int s = 1; s < W; ++s) av[s - 1] = A[(int64_t)s * n + g.i];
+        }
+        // a_ji of slot s lives in row j at the opposite slot: slots E,NE,N <-> W,SW,S
+#pragma unroll
+        for (int s = 0; s < 3; ++s) as[s][g.self] = av[s + 3];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 3; ++s) at[s] = as[s][g.nb[s]];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 3; ++s) as[s][g.self] = av[s];
+        __syncthreads();
+#pragma unroll
+        for (int s = 3; s < 6; ++s) at[s] = as[s - 3][g.nb[s]];
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const double a = av[s];
+            const double d = ex[s] ? fmax(0.0, fmax(a, at[s])) : 0.0;   // d_ij = max(0, a_ij, a_ji)
+            dsum += d;
+            double l = dt * (a - d);
+            if (Nm && g.inside) l += dt * Nm[(int64_t)(s + 1) * n + g.i];
+            lv[s] = l;
+            dv[s] = d;
+            rs += l;
+        }
+        if (g.inside) {
+            const double mli = ml[g.i];
+            double ld = mli + dt * (a0 + dsum);                         // d_ii = -sum_j d_ij
+            if (Nm) ld += dt * Nm[g.i];
+            rs += ld;
+            dg = ld;
+            rdg = 1.0 / dg;
+            xi = u[g.i];
+            bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+        }
     }
     double bmax = 0.0, rsmin = INFINITY;
     if (g.owned) {
         double* L = L_ + moff;
-        double* D = D_ + moff;
         L[g.i] = dg;
-        D[g.i] = -dsum;
 #pragma unroll
-        for (int s = 1; s < W; ++s) {
-            L[(int64_t)s * n + g.i] = lv[s - 1];
-            D[(int64_t)s * n + g.i] = dv[s - 1];
+        for (int s = 1; s < W; ++s) L[(int64_t)s * n + g.i] = lv[s - 1];
+        if constexpr (!PRE) {
+            double* D = D_ + moff;
+            D[g.i] = -dsum;
+#pragma unroll
+            for (int s = 1; s < W; ++s) D[(int64_t)s * n + g.i] = dv[s - 1];
         }
         b_[voff + g.i] = bv;
         bmax = fabs(bv);
@@ -616,6 +639,46 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
         p[wg] = rmax;
         p[2 * FEMFCT_MAX_PARTIALS + wg] = bmax;
         p[3 * FEMFCT_MAX_PARTIALS + wg] = rsmin;
+    }
+}
+
+// The low-order operator of every entry of a pre-assembled sequence, once before the sweep (FEMFCT_PREBUILD_LOW):
+// L_k = M_L + dt (A_k - D_k) and D_k depend on the control only.  The expressions and their order are those of
+// k_tile_build_jacobi (no non-flux matrix), so the bits are the same; a_ji is read from the neighbour's row.
+// Structured mesh in vertex order; blockIdx.y = sequence entry (as k_ops_solidbody writes them).
+__global__ void __launch_bounds__(256)
+k_low_seq(int n, int N, const double* __restrict__ A_, const double* __restrict__ ml, double dt, double* __restrict__ L_,
+          double* __restrict__ D_) {
+    constexpr int W = 7;
+    const int64_t off = (int64_t)blockIdx.y * W * n;
+    const double* A = A_ + off;
+    double* L = L_ + off;
+    double* D = D_ + off;
+    const int dx[6] = {1, 1, 0, -1, -1, 0}, dy[6] = {0, 1, 1, 0, -1, -1};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int gx = i % N, gy = i / N;
+        double av[W - 1], at[W - 1];
+        bool ex[W - 1];
+        const double a0 = A[i];
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const int nx = gx + dx[s], ny = gy + dy[s];
+            ex[s] = nx >= 0 && nx < N && ny >= 0 && ny < N;
+            av[s] = A[(int64_t)(s + 1) * n + i];
+            // a_ji of slot s lives in row j at the opposite slot: slots E,NE,N <-> W,SW,S
+            at[s] = ex[s] ? A[(int64_t)(s < 3 ? s + 4 : s - 2) * n + ny * N + nx] : 0.0;
+        }
+        double dsum = 0.0;
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const double a = av[s];
+            const double d = ex[s] ? fmax(0.0, fmax(a, at[s])) : 0.0;   // d_ij = max(0, a_ij, a_ji)
+            dsum += d;
+            L[(int64_t)(s + 1) * n + i] = dt * (a - d);
+            D[(int64_t)(s + 1) * n + i] = d;
+        }
+        L[i] = ml[i] + dt * (a0 + dsum);                                // d_ii = -sum_j d_ij
+        D[i] = -dsum;
     }
 }
 
@@ -799,13 +862,14 @@ template <int GEOM>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, const double* __restrict__ b_,
                        const double* __restrict__ ymid_, const double* __restrict__ yold_, int K, CheOmegas om,
-                       double md_scale, const double* __restrict__ D_, const double* __restrict__ ulow_,
+                       double md_scale, MatRef D_ref, const double* __restrict__ ulow_,
                        const double* __restrict__ ml, double dt, VecRef out_ref, int64_t out_bstride, EndArgs e) {
     constexpr int W = 7, HH = 12;
     __shared__ double ys[3][TILE_L * TILE_LD];
     __shared__ double su[TILE_L * TILE_LD], srp[TILE_L * TILE_LD], srm[TILE_L * TILE_LD];
     const int bz = blockIdx.z;
-    const int64_t moff = (int64_t)bz * W * n, voff = (int64_t)bz * n;
+    const int64_t voff = (int64_t)bz * n;
+    const double* D_ = mat_ptr(D_ref, bz);     // the step's D (one of the pre-built sequence, or the workspace's)
     const TileGeom g = tile_geom<TILE_L - 2 * HH, HH>(N);
     double mv[W - 1], dv[W - 1], md = 1.0, rmd = 1.0, bv = 0.0, ym = 0.0, yo = 0.0, ui = 0.0, mli = 1.0;
 #pragma unroll
@@ -825,8 +889,6 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         bv = b_[voff + g.i];
         ym = ymid_[voff + g.i];
         yo = yold_[voff + g.i];
-#pragma unroll
-        for (int s = 1; s < W; ++s) dv[s - 1] = D_[moff + (int64_t)s * n + g.i];
         ui = ulow_[voff + g.i];
         mli = ml[g.i];
     }
@@ -837,6 +899,12 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
     srm[g.self] = 1.0;
     __syncthreads();
     step_log_early(e);        // (behind this kernel's own loads; its round trip is covered by the Chebyshev iterations)
+    // D is first needed by the fluxes: requested behind the log copy (which waits for every load in flight) so that a
+    // pre-built D_k, an HBM round trip behind the level counter, is covered by the iterations too
+    if (g.inside) {
+#pragma unroll
+        for (int s = 1; s < W; ++s) dv[s - 1] = D_[(int64_t)s * n + g.i];
+    }
     int io = 0, im = 1, in_ = 2;
     for (int k = 0; k < K; ++k) {
         const double* ymd = ys[im];
@@ -908,7 +976,7 @@ bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch) {
 }
 
 int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const double* in_mid, const double* in_old,
-                                        int k_first, int k_last, const double* omegas, double md_scale, const double* D,
+                                        int k_first, int k_last, const double* omegas, double md_scale, MatRef D,
                                         const double* ulow, double dt, VecRef out, int64_t out_bstride, int32_t batch,
                                         bool fuse_end) {
     const int K = k_last - k_first + 1;
@@ -1007,19 +1075,34 @@ bool femfct_tile_big(const femfct_ctx* ctx, const TilePlan& pl) {
 
 // launch 0 with the operator construction fused in (latency regime; needs >= 2 launches in total because
 // ||b|| is reduced by launch 1).  Later launches: femfct_enqueue_tile_jacobi(..., bn_launch = 1, g_build = tiles^2).
+// pre: A is the pre-built L_k sequence (femfct_enqueue_low_seq; Nm must be null), D_k is not stored.
 int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, MatRef A, const double* Nm, int32_t nshared,
                                      VecRef rhs, int64_t rhs_bstride, VecRef u_n, int64_t u_bstride, double dt,
-                                     int32_t batch) {
+                                     int32_t batch, bool pre) {
+    if (pre && Nm) return femfct_fail(ctx, FEMFCT_ERR_INVALID, "pre-built low-order operator with a non-flux matrix");
     dim3 grid(pl.tiles, pl.tiles, batch);
     femfct_prof_begin(ctx, KC_JACOBI);
-#define TB(HH) hipLaunchKernelGGL((k_tile_build_jacobi<HH>), grid, dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, A, Nm,  \
-                                  nshared, rhs, rhs_bstride, u_n, u_bstride, ctx->d_ml, dt, ctx->d_L, ctx->d_D, ctx->d_b, \
-                                  ctx->d_xb, ctx->d_part, ctx->d_ctl, pl.K)
+#define TB_(HH, P) hipLaunchKernelGGL((k_tile_build_jacobi<HH, P>), grid, dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, A, Nm,  \
+                                      nshared, rhs, rhs_bstride, u_n, u_bstride, ctx->d_ml, dt, ctx->d_L, ctx->d_D, ctx->d_b, \
+                                      ctx->d_xb, ctx->d_part, ctx->d_ctl, pl.K)
+#define TB(HH) do { if (pre) TB_(HH, 1); else TB_(HH, 0); } while (0)
     switch (pl.H) {
         case 8: TB(8); break; case 9: TB(9); break; case 10: TB(10); break;
         case 11: TB(11); break; case 12: TB(12); break; default: TB(13); break;
     }
 #undef TB
+#undef TB_
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
+// L_k and D_k of `entries` consecutive sequence entries of A (k_low_seq); structured mesh in vertex order
+int femfct_enqueue_low_seq(femfct_ctx* ctx, const double* A, double* L, double* D, int32_t entries, double dt) {
+    if (!ctx->implicit_cols || ctx->W != 7 || (int64_t)ctx->N * ctx->N != ctx->n || entries < 1 || entries > 65535)
+        return femfct_fail(ctx, FEMFCT_ERR_INVALID, "low-order sequence: structured mesh in vertex order only");
+    femfct_prof_begin(ctx, KC_ASSEMBLE);
+    hipLaunchKernelGGL(k_low_seq, dim3((ctx->n + 255) / 256, entries), dim3(256), 0, ctx->stream, ctx->n, ctx->N, A, ctx->d_ml,
+                       dt, L, D);
     femfct_prof_end(ctx);
     return FEMFCT_OK;
 }

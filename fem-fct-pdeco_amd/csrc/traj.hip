@@ -24,15 +24,28 @@ int femfct_enqueue_ops_solidbody(femfct_ctx* ctx, const double* Arot, VecRef c_r
                                  double sigma, double rot_scale, double bx, double by, double* A, int32_t batch,
                                  int32_t levels = 1);
 
+// Whether the tile step's first launch would take a pre-built low-order operator (femfct_enqueue_step_op: fused build,
+// fused du/dt and Chebyshev-flux tail; no non-flux matrix in the solid-body sweeps).
+static bool prebuild_low_wanted(const femfct_ctx* ctx, int32_t batch) {
+    TilePlan tp;
+    return ctx->prebuild_low && ctx->fuse_build && ctx->fuse_dudt && ctx->structured && ctx->implicit_cols && ctx->W == 7 &&
+           ctx->solver != FEMFCT_SOLVER_BICGSTAB && !femfct_mesh_step_wanted(ctx, batch) && !femfct_tile4_wanted(ctx, batch) &&
+           femfct_tile_plan(ctx, &tp, false, 0, batch) && !femfct_tile_big(ctx, tp) && femfct_cheb_flux_fusable(ctx, batch);
+}
+
 // The solid-body operator depends on the control only, which is given for the whole sweep: assemble the
 // matrices of all time levels in one launch before the sweep (HBM is large: Nt * 7n doubles per control
 // trajectory, 92 MB at C2) instead of one small dependent launch per step.  Returns false (per-step
 // assembly) when the sequence would not fit the configured cap or the launch grid.
+// So does the low-order operator L_k = M_L + dt (A_k - D_k), D_k of the latency-regime tile step: built from the
+// sequence by a second launch (2 x 92 MB more at C2, under the same cap) unless FEMFCT_PREBUILD_LOW=0; without it
+// (or without room for it) the step's first launch builds them as before.
 static bool solidbody_preassemble(femfct_ctx* ctx, const double* Arot, const double* c_traj, int32_t c_shared,
                                   int64_t tstride, int32_t c_level0, double eps, double sigma, double rot_scale, double bx,
-                                  double by, int32_t num_steps, int32_t batch, MatRef* out) {
+                                  double by, int32_t num_steps, int32_t batch, double dt, MatRef* out) {
     const int32_t members = c_shared ? 1 : batch;
     const size_t count = (size_t)members * num_steps * ctx->W * ctx->n;
+    ctx->low_src = nullptr;     // d_trAall is about to change: no pre-built L / D matches it
     if (!ctx->preassemble || (double)count * 8.0 > ctx->preassemble_max_bytes) return false;
     if ((int64_t)members * num_steps > 65535) return false;
     if (count > ctx->trAall_count) {
@@ -47,6 +60,21 @@ static bool solidbody_preassemble(femfct_ctx* ctx, const double* Arot, const dou
                                  rot_scale, bx, by, ctx->d_trAall, members, num_steps);
     const int64_t wn = (int64_t)ctx->W * n;
     *out = MatRef{ctx->d_trAall, ctx->d_level, wn, 0, c_shared ? 0 : wn * num_steps};
+    if (prebuild_low_wanted(ctx, batch) && (double)count * 3.0 * 8.0 <= ctx->preassemble_max_bytes) {
+        if (2 * count > ctx->lowall_count) {
+            femfct_drop_graphs(ctx);
+            if (ctx->d_lowall) hipFree(ctx->d_lowall);
+            ctx->d_lowall = nullptr; ctx->lowall_count = 0;
+            if (hipMalloc((void**)&ctx->d_lowall, sizeof(double) * 2 * count) != hipSuccess) (void)hipGetLastError();
+            else ctx->lowall_count = 2 * count;
+        }
+        if (ctx->d_lowall &&
+            femfct_enqueue_low_seq(ctx, ctx->d_trAall, ctx->d_lowall, ctx->d_lowall + count, members * num_steps, dt) == FEMFCT_OK) {
+            ctx->low_src = ctx->d_trAall;
+            ctx->low_dt = dt;
+            ctx->low_doff = count;
+        }
+    }
     return true;
 }
 int femfct_enqueue_mass_diff(femfct_ctx* ctx, VecRef a, int64_t a_bstride, VecRef b, int64_t b_bstride, double* out,
@@ -174,7 +202,7 @@ int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const 
         ctx->last_rot_geom = rotg != 0;
         if (!inl)
             pre = solidbody_preassemble(ctx, Arot, c_traj, c_shared, tstride, 1, eps, -1.0, rot_scale, bx, by, num_steps,
-                                        batch, &Aall);
+                                        batch, dt, &Aall);
         return FEMFCT_OK;
     };
     auto step = [&](int budget, int, int reps) {
@@ -237,7 +265,7 @@ int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const doub
         // level counter n uses the control of level n (finaltime.py:213): sequence entry n
         if (!inl)
             pre = solidbody_preassemble(ctx, Arot, c_traj, c_shared, tstride, 0, eps, +1.0, rot_scale, bx, by, num_steps,
-                                        batch, &Aall);
+                                        batch, dt, &Aall);
         // terminal condition: p(T) = uhat_T - u(T) (finaltime.py:201) or 0 (alltime.py:232)
         for (int32_t b = 0; b < batch; ++b) {
             double* pT = p_traj + b * tstride + (int64_t)num_steps * n;
