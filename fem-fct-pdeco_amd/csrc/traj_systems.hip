@@ -250,37 +250,76 @@ int femfct_nonlinear_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const dou
     return nonlinear_forward(ctx, Aw_ell, Ctl::traj(c_traj, c_shared), u_traj, num_steps, dt, eps, batch);
 }
 
-// helpers.py:968-1038: p(T) = uhat_T - u(T); FCT_alg_ref(-Mat_p, 0, p_{n+1}, non_flux_mat = M_u2(u_n) - M)
-int femfct_nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat_T,
-                             double* p_traj, int32_t num_steps, double dt, double eps, int32_t batch) {
-    FEMFCT_ENTER(ctx);
+// helpers.py:968-1038: p(T) = uhat_T - u(T); FCT_alg_ref(-Mat_p, 0, p_{n+1}, non_flux_mat = M_u2(u_n) - M).
+// alltime (nonlinear_FCT_PDECO_alltime.py:198-216 with the HEAD operators): uhat is a trajectory (batch stride ts, or 0 when
+// uhat_shared), p(T) = 0 and the step to level n carries rhs = M (uhat_n - u_n) (FCT_alg_ref scales rhs by dt itself,
+// helpers.py:1780).  The all-time sweep is a kind of its own (16): its graphs never meet a final-time key, and its
+// budgets leave those of the final-time sweep (kind 11) as they were.  Both launch the same kernels per step.
+static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat,
+                             int32_t uhat_shared, bool alltime, double* p_traj, int32_t num_steps, double dt, double eps,
+                             int32_t batch) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
-    ARG_TRY(ctx, Aw_ell && u_traj && uhat_T && p_traj, "null argument");
+    ARG_TRY(ctx, Aw_ell && u_traj && uhat && p_traj, "null argument");
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     const int64_t n = ctx->n, wn = (int64_t)ctx->W * n, ts = (int64_t)(num_steps + 1) * n;
+    const int kind = alltime ? 16 : 11;
+    const int32_t shared = uhat_shared ? 1 : 0;
     Lv L{ctx, ctx->d_level, n};
     auto begin = [&]() {
         for (int32_t b = 0; b < batch; ++b) femfct_enqueue_axpby(ctx, wn, eps, ctx->d_Ad, 1.0, Aw_ell, ctx->d_trA + b * wn);
-        return terminal_diff(ctx, uhat_T, u_traj, p_traj, num_steps, batch);
+        if (alltime) {      // pk = np.zeros(vec_length) (nonlinear_FCT_PDECO_alltime.py:200)
+            for (int32_t b = 0; b < batch; ++b)
+                HIP_TRY(ctx, hipMemsetAsync(p_traj + b * ts + (int64_t)num_steps * n, 0, sizeof(double) * n, ctx->stream));
+            return (int)FEMFCT_OK;
+        }
+        return terminal_diff(ctx, uhat, u_traj, p_traj, num_steps, batch);
     };
     auto step = [&](int budget, int, int reps) {
-        auto key = KEY((uint64_t)11, key_bits(Aw_ell), key_bits(u_traj), key_bits(uhat_T), key_bits(p_traj),
+        auto key = KEY((uint64_t)kind, key_bits(Aw_ell), key_bits(u_traj), key_bits(uhat), key_bits(p_traj),
                        key_bits(num_steps), key_bits(dt), key_bits(eps), key_bits(batch), key_bits((int32_t)budget),
                        key_bits(ctx->rel_tol));
+        if (alltime) key.push_back(key_bits(shared));
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             WMassSpec ws;  // Mat_rhs = M_u2(u_n) - M (helpers.py:1032-1034)
             ws.alpha = -1.0; ws.beta = 1.0; ws.f1 = L(u_traj, 0); ws.f2 = L(u_traj, 0); ws.f1_bs = ws.f2_bs = ts;
-            femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trN, batch);
+            VecRef rhs = make_ref(nullptr);
+            int64_t rhs_bs = 0;
+            if (alltime) {          // assemble((uhat_n - u_n)*v*dx) (:209-210) rides in the weighted mass's launch
+                LoadSpec lp;
+                lp.s3 = 1.0; lp.ea = L(uhat, 0); lp.ea_bs = shared ? 0 : ts; lp.eb = L(u_traj, 0); lp.eb_bs = ts;
+                FormGroup fg(ctx);
+                fg.weighted_mass(ws, ctx->d_trN, batch);
+                fg.load(lp, ctx->d_trRhs, batch);
+                int r = fg.launch();
+                if (r != FEMFCT_OK) return r;
+                rhs = make_ref(ctx->d_trRhs);
+                rhs_bs = n;
+            } else {
+                femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trN, batch);
+            }
             femfct_request_fused_end(ctx, -1, false);
-            int r = femfct_enqueue_step_ref(ctx, ctx->d_trA, ctx->d_trN, 0, make_ref(nullptr), 0, L(p_traj, 1), ts, dt,
+            int r = femfct_enqueue_step_ref(ctx, ctx->d_trA, ctx->d_trN, 0, rhs, rhs_bs, L(p_traj, 1), ts, dt,
                                             L(p_traj, 0), ts, batch, budget);
             if (r != FEMFCT_OK) return r;
             return femfct_enqueue_step_end(ctx, -1, batch, false);
         });
     };
-    ctx->kind_fullrows.insert(11);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
-    return femfct_run_sweep(ctx, 11, num_steps, batch, num_steps - 1, false, begin, step);
+    ctx->kind_fullrows.insert(kind);    // (diffusion / reaction terms: rows with both entries of a pair from the start)
+    return femfct_run_sweep(ctx, kind, num_steps, batch, num_steps - 1, false, begin, step);
+}
+
+int femfct_nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat_T,
+                             double* p_traj, int32_t num_steps, double dt, double eps, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return nonlinear_adjoint(ctx, Aw_ell, u_traj, uhat_T, 0, false, p_traj, num_steps, dt, eps, batch);
+}
+
+int femfct_nonlinear_adjoint_alltime(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat_traj,
+                                     int32_t uhat_shared, double* p_traj, int32_t num_steps, double dt, double eps,
+                                     int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return nonlinear_adjoint(ctx, Aw_ell, u_traj, uhat_traj, uhat_shared, true, p_traj, num_steps, dt, eps, batch);
 }
 
 // ------------------------------------------------------------------ advective Schnakenberg

@@ -402,7 +402,17 @@ class Context:
         check(self.handle, lib.femfct_nonlinear_forward_ct(self.handle, dptr(Aw), dptr(c_traj), int(bool(c_shared)), dptr(u),
                                                            int(num_steps), float(dt), float(eps), int(batch)))
 
-    def nonlinear_adjoint(self, Aw, u, uhat_T, p, num_steps, dt, eps, batch=1):
+    def nonlinear_adjoint(self, Aw, u, uhat_T, p, num_steps, dt, eps, batch=1, alltime=False, uhat_shared=False):
+        """alltime=False: final-time misfit, uhat_T n values per member.  alltime=True: all-time misfit
+        (nonlinear_FCT_PDECO_alltime.py:198-216), uhat_T a target trajectory per member ((num_steps+1)*n values, or one
+        for the whole batch with uhat_shared), p(T) = 0."""
+        if alltime:
+            check(self.handle, lib.femfct_nonlinear_adjoint_alltime(self.handle, dptr(Aw), dptr(u), dptr(uhat_T),
+                                                                    int(bool(uhat_shared)), dptr(p), int(num_steps),
+                                                                    float(dt), float(eps), int(batch)))
+            return
+        if uhat_shared:
+            raise ValueError("uhat_shared: only the all-time sweep takes a shared target")
         check(self.handle, lib.femfct_nonlinear_adjoint(self.handle, dptr(Aw), dptr(u), dptr(uhat_T), dptr(p),
                                                         int(num_steps), float(dt), float(eps), int(batch)))
 

@@ -4,6 +4,9 @@
   Schnak_FCT_PDECO_refactored.py:122-259           "schnak"     (two states, final-time misfit)
   chemotaxis_FCT_PDECO_AT_refactored.py:112-290    "chtxs"      (two states, all-time misfit)
 
+Each problem also runs with the other misfit (``optim=``); "nonlinear" with ``optim="alltime"`` and
+``control_per_step=True`` is nonlinear_FCT_PDECO_alltime.py (p(T) = 0, misfit load in every adjoint step).
+
 The loop, its constants, the line-search bookkeeping (fail counters, restarts, the control backup)
 and the order of the floating-point operations of the pointwise gradient follow the scripts; states,
 adjoints, controls and targets stay in HBM and only scalars (costs, norms) reach the host.
@@ -146,7 +149,8 @@ class SystemPDECO:
 
     def _adjoint(self, u, v, p, q, c, tg):
         if self.problem == "nonlinear":
-            self.ctx.nonlinear_adjoint(self.Aw, u, tg[0], p, self.Nt, self.dt, self.eps)
+            self.ctx.nonlinear_adjoint(self.Aw, u, tg[0], p, self.Nt, self.dt, self.eps,
+                                       alltime=self.P["optim"] == "alltime")
         elif self.problem == "schnak":
             self.ctx.schnak_adjoint(self.AwT, u, v, tg[0], tg[1], p, q, self.Nt, self.dt, self.par,
                                     alltime=self.P["optim"] == "alltime", wind_scale=self.wscale_adj)

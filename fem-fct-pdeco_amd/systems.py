@@ -216,15 +216,24 @@ def solve_nonlinear_equation(control, var1, var2, V, nodes, num_steps, dt, dof_n
     return var1, None
 
 
-def solve_adjoint_nonlinear_equation(uk, uhat_T, pk, T, V, nodes, num_steps, dt, dof_neighbors):
-    """helpers.py:968-1038: fills ``pk`` (terminal condition included) and returns it."""
+def solve_adjoint_nonlinear_equation(uk, uhat_T, pk, T, V, nodes, num_steps, dt, dof_neighbors, optim="finaltime"):
+    """helpers.py:968-1038 (``optim="finaltime"``, the reference's signature and behaviour): fills ``pk`` (terminal
+    condition included) and returns it.  ``optim="alltime"`` (extension, nonlinear_FCT_PDECO_alltime.py:198-216 with
+    the HEAD operators): ``uhat_T`` is the target trajectory ((num_steps+1)*nodes values), p(T) = 0 and the step to
+    level n carries the misfit load ``assemble((uhat_n - u_n)*v*dx)``."""
+    if optim not in ("alltime", "finaltime"):
+        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+    alltime = optim == "alltime"
+    want = (num_steps + 1) * nodes if alltime else nodes
+    if np.asarray(uhat_T).size != want:
+        raise ValueError(f"optim='{optim}': target has {np.asarray(uhat_T).size} values, expected {want}")
     S = _system(V)
     eps, _, wind = get_nonlinear_eqns_params()
     Aw, _ = S.convection(wind, "nonlinear")
     B = _Bufs(S)
     try:
         p = B.up(pk)
-        S.ctx.nonlinear_adjoint(Aw, B.up(uk), B.up(uhat_T), p, num_steps, dt, eps)
+        S.ctx.nonlinear_adjoint(Aw, B.up(uk), B.up(uhat_T), p, num_steps, dt, eps, alltime=alltime)
         B.down(p, pk)
     finally:
         B.free()

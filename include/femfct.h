@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
+#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct, femfct_nonlinear_adjoint_alltime (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
 
 typedef struct femfct_ctx femfct_ctx;
 
@@ -350,6 +350,14 @@ int femfct_schnak_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const double
                              const double* par, double rescaling, int32_t batch);
 int femfct_chtxs_forward_ct(femfct_ctx* ctx, const double* c_traj, int32_t c_shared, double* u_traj, double* v_traj,
                             int32_t num_steps, double dt, const double* par, double rescaling, int32_t batch);
+/* all-time misfit of the nonlinear equation (nonlinear_FCT_PDECO_alltime.py:198-216 with the HEAD operators of
+ * helpers.py:1017-1037): p(T) = 0; for n = Nt-1..0:
+ *   p_n = FCT_alg_ref(-Mat_p, M (uhat_n - u_n), p_{n+1}, non_flux_mat = M_u2(u_n) - M)
+ * uhat_traj: (num_steps+1)*n doubles per member (batch stride (num_steps+1)*n), uhat_shared != 0: one trajectory for
+ * the whole batch. */
+int femfct_nonlinear_adjoint_alltime(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj,
+                                     const double* uhat_traj, int32_t uhat_shared, double* p_traj,
+                                     int32_t num_steps, double dt, double eps, int32_t batch);
 /* BiCGStab diagnostics of the most recent sweep that used it: info_host[step*batch + b] */
 int femfct_traj_krylov_info(femfct_ctx* ctx, femfct_step_info* info_host, int32_t num_steps, int32_t batch);
 

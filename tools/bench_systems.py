@@ -84,6 +84,8 @@ t = timeit(lambda: ctx.nonlinear_forward(Awn, cn, u, Nt, 1e-3, eps))
 print(f"nonlinear forward    : {Nt / t:8.0f} steps/s")
 t = timeit(lambda: ctx.nonlinear_adjoint(Awn, u, uh, p, Nt, 1e-3, eps))
 print(f"nonlinear adjoint    : {Nt / t:8.0f} steps/s")
+t = timeit(lambda: ctx.nonlinear_adjoint(Awn, u, uh, p, Nt, 1e-3, eps, alltime=True))    # uh: a target trajectory
+print(f"nonlinear adjoint (all-time): {Nt / t:8.0f} steps/s")
 S.close()
 
 # ---------------------------------------------------------------------------------------------
