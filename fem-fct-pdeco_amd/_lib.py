@@ -20,6 +20,7 @@ ORDER_VERTEX, ORDER_FENICS = 0, 1
 SOLVER_JACOBI, SOLVER_BICGSTAB = 0, 1
 REGIME_ROWS, REGIME_STRIPS, REGIME_TILE32, REGIME_PATCH64, REGIME_MESH = 0, 1, 2, 3, 4
 ABI_VERSION = 5
+MAX_TRIALS = 16          # FEMFCT_MAX_TRIALS: Armijo trials per femfct_linear_trial_costs / femfct_source_trials call
 
 
 class FemFctError(RuntimeError):
@@ -137,6 +138,8 @@ SIGNATURES = {
     "femfct_l2_norm_sq_Omega": (C.c_int, [_p, _p, _p, _p, _i]),
     "femfct_cost_functional": (C.c_int, [_p, _p, _p, _p, _i, _i, _d, _d, _i, _p, _p, _p, _i]),
     "femfct_project_control": (C.c_int, [_p, _p, _d, _p, _d, _d, _p, C.c_int64]),
+    "femfct_linear_trial_costs": (C.c_int, [_p, _p, _p, _p, _p, _p, _d, _i, _d, _d, _d, _i, _d, _i, _p, _p]),
+    "femfct_source_trials": (C.c_int, [_p, _p, _p, _p, _d, _i, _d, _d, C.c_int64, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

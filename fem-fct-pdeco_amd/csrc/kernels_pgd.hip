@@ -3,12 +3,15 @@
 //   L2_norm_sq_Q / L2_norm_sq_Omega   /root/reference/helpers.py:330-381
 //   cost_functional                   /root/reference/helpers.py:383-441
 //   update_control (clip)             /root/reference/helpers.py:1666-1667
+//   Armijo trial batches              helpers.py:1681-1708, advection_FCT_PDECO_alltime_exact.py:282-297
 //
 // Quadratic forms phi^T M phi are summed with a fixed reduction tree (per-thread row
 // sums -> wave64 butterflies -> LDS -> per-block partials -> one block), no atomics:
 // bitwise reproducible.
 #include "femfct_internal.h"
 #include "device_utils.h"
+
+#include <utility>
 
 namespace {
 
@@ -73,6 +76,131 @@ __global__ void k_descent_pointwise(int64_t count, double beta, const double* __
     for (; k < count; k += stride) {
         const double t = y ? (x[k] * y[k]) / divisor : scale * x[k];
         out[k] = -(beta * c[k] - t);
+    }
+}
+
+// All K Armijo trials of the linear-increment search (advection_FCT_PDECO_alltime_exact.py:282-297, helpers.py:1681-1708)
+// in one pass over u, w, uhat, c, d.  Trial t has s_t = s0 * (1 / 2^t), c_t = clip(c + s_t d) and the state u + s_t w;
+// for every (level, block) the launch writes the three k_quadform partials the materialised path would compute:
+//   misfit   phi = (u + s_t w) - uhat   (every level; level Nt only, against the n-value target, when finaltime)
+//   control  phi = c_t - 0.0
+//   dist     phi = c_t - c
+// Rows, expressions and order are k_quadform's (block_rows partition, diagonal then slots 1..W-1, the same wave64 /
+// LDS tree), so k_reduce_levels over these partials gives the bits of femfct_cost_functional / femfct_l2_norm_sq_Q on
+// materialised trials.  Levels are strided over gridDim.y (no 65535 cap).  Partials: misfit at [t*plen_m + l*G + blk]
+// (plen_m = G when finaltime, l = 0), control / dist at [t*levels*G + l*G + blk].
+template <int K>
+__global__ void __launch_bounds__(256) k_linear_trials(int n, int W, const int32_t* __restrict__ cols,
+                                                       const double* __restrict__ M, const double* __restrict__ u,
+                                                       const double* __restrict__ w, const double* __restrict__ uhat,
+                                                       const double* __restrict__ c, const double* __restrict__ d,
+                                                       double s0, double lo, double hi, int levels, int finaltime,
+                                                       double* __restrict__ part_m, double* __restrict__ part_c,
+                                                       double* __restrict__ part_d) {
+    __shared__ double smem[3 * K * 4];      // 3K sums x up to 4 waves (blockDim <= 256)
+    const int G = gridDim.x;
+    const int64_t plen = (int64_t)levels * G, plen_m = finaltime ? G : plen;
+    const int nw = (blockDim.x + WAVE - 1) / WAVE, wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    double s[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) s[t] = s0 * (1.0 / (double)(1 << t));
+    RowRange rr = block_rows(n);
+    for (int lvl = blockIdx.y; lvl < levels; lvl += gridDim.y) {
+        const bool mis = !finaltime || lvl == levels - 1;         // uniform over the block
+        const int64_t off = (int64_t)lvl * n;
+        const double *ul = u + off, *wl = w + off, *cl = c + off, *dl = d + off;
+        const double* hl = uhat + (finaltime ? 0 : off);
+        double sm[K], sc[K], sd[K];
+#pragma unroll
+        for (int t = 0; t < K; ++t) sm[t] = sc[t] = sd[t] = 0.0;
+        for (int i = rr.begin + threadIdx.x; i < rr.end; i += blockDim.x) {
+            double am[K], ac[K], ad[K];
+            const double mi = M[i], ci = cl[i], di = dl[i];
+            const double ui = mis ? ul[i] : 0.0, wi = mis ? wl[i] : 0.0, hi_ = mis ? hl[i] : 0.0;
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+                const double ct = fmin(fmax(ci + s[t] * di, lo), hi);
+                am[t] = mi * ((ui + s[t] * wi) - hi_);
+                ac[t] = mi * (ct - 0.0);
+                ad[t] = mi * (ct - ci);
+            }
+            for (int k = 1; k < W; ++k) {
+                const int64_t idx = (int64_t)k * n + i;
+                const int j = cols[idx];
+                const double mk = M[idx], cj = cl[j], dj = dl[j];
+                const double uj = mis ? ul[j] : 0.0, wj = mis ? wl[j] : 0.0, hj = mis ? hl[j] : 0.0;
+#pragma unroll
+                for (int t = 0; t < K; ++t) {
+                    const double ct = fmin(fmax(cj + s[t] * dj, lo), hi);
+                    am[t] += mk * ((uj + s[t] * wj) - hj);
+                    ac[t] += mk * (ct - 0.0);
+                    ad[t] += mk * (ct - cj);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+                const double ct = fmin(fmax(ci + s[t] * di, lo), hi);
+                sm[t] += ((ui + s[t] * wi) - hi_) * am[t];
+                sc[t] += (ct - 0.0) * ac[t];
+                sd[t] += (ct - ci) * ad[t];
+            }
+        }
+        // block_reduce's tree for each of the 3K sums: wave butterflies, then the waves in order from 0.0
+#pragma unroll
+        for (int t = 0; t < K; ++t) {
+            sm[t] = wave_reduce(sm[t], OpSum());
+            sc[t] = wave_reduce(sc[t], OpSum());
+            sd[t] = wave_reduce(sd[t], OpSum());
+        }
+        if (nw > 1) {
+            __syncthreads();   // smem reuse across levels
+            if (lane == 0) {
+#pragma unroll
+                for (int t = 0; t < K; ++t) {
+                    smem[(3 * t) * 4 + wid] = sm[t];
+                    smem[(3 * t + 1) * 4 + wid] = sc[t];
+                    smem[(3 * t + 2) * 4 + wid] = sd[t];
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+                double rm = 0.0, rc = 0.0, rd = 0.0;
+                for (int q = 0; q < nw; ++q) {
+                    rm = rm + smem[(3 * t) * 4 + q];
+                    rc = rc + smem[(3 * t + 1) * 4 + q];
+                    rd = rd + smem[(3 * t + 2) * 4 + q];
+                }
+                sm[t] = rm; sc[t] = rc; sd[t] = rd;
+            }
+        }
+        if (threadIdx.x == 0) {
+            const int64_t pl = (int64_t)lvl * G + blockIdx.x;
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+                if (mis) part_m[t * plen_m + (finaltime ? blockIdx.x : pl)] = sm[t];
+                part_c[t * plen + pl] = sc[t];
+                part_d[t * plen + pl] = sd[t];
+            }
+        }
+    }
+}
+
+// Resolve-mode trials: c_out[t] = clip(c + s_t d) as k_clip_axpy, src_out[t] = g + c_out[t] as k_axpby(1, g, 1, c_t)
+// (g NULL: src_out[t] = c_out[t]; src_out NULL: no sources), t < K, each block member count doubles long.
+__global__ void k_source_trials(int64_t count, int K, const double* __restrict__ c, const double* __restrict__ d,
+                                const double* __restrict__ g, double s0, double lo, double hi,
+                                double* __restrict__ c_out, double* __restrict__ src_out) {
+    int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; k < count; k += stride) {
+        const double ck = c[k], dk = d[k], gk = g ? g[k] : 0.0;
+        for (int t = 0; t < K; ++t) {
+            const double s = s0 * (1.0 / (double)(1 << t));
+            const double ct = fmin(fmax(ck + s * dk, lo), hi);
+            c_out[t * count + k] = ct;
+            if (src_out) src_out[t * count + k] = g ? 1.0 * gk + 1.0 * ct : ct;
+        }
     }
 }
 
@@ -195,6 +323,85 @@ int femfct_project_control(femfct_ctx* ctx, const double* c_dev, double s, const
     if (g < 1) g = 1;
     hipLaunchKernelGGL(k_clip_axpy, dim3((unsigned)g), dim3(bs), 0, ctx->stream, count, c_dev, s, d_dev, c_lower,
                        c_upper, out_dev);
+    return FEMFCT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- Armijo trial batches
+namespace {
+
+template <int K>
+void launch_linear_trials(dim3 grid, dim3 block, hipStream_t st, int n, int W, const int32_t* cols, const double* M,
+                          const double* u, const double* w, const double* uhat, const double* c, const double* d,
+                          double s0, double lo, double hi, int levels, int finaltime, double* pm, double* pc, double* pd) {
+    hipLaunchKernelGGL(k_linear_trials<K>, grid, block, 0, st, n, W, cols, M, u, w, uhat, c, d, s0, lo, hi, levels,
+                       finaltime, pm, pc, pd);
+}
+
+using LinearTrialsLaunch = void (*)(dim3, dim3, hipStream_t, int, int, const int32_t*, const double*, const double*,
+                                    const double*, const double*, const double*, const double*, double, double, double,
+                                    int, int, double*, double*, double*);
+
+template <int... Ks>
+constexpr LinearTrialsLaunch linear_trials_table(int K, std::integer_sequence<int, Ks...>) {
+    constexpr LinearTrialsLaunch tab[] = {launch_linear_trials<Ks + 1>...};
+    return tab[K - 1];
+}
+
+}  // namespace
+
+extern "C" {
+
+int femfct_linear_trial_costs(femfct_ctx* ctx, const double* u_dev, const double* w_dev, const double* uhat_dev,
+                              const double* c_dev, const double* d_dev, double s0, int32_t K, double c_lower,
+                              double c_upper, double beta, int32_t num_steps, double dt, int32_t finaltime,
+                              double* J_host, double* dist_host) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx && ctx->n > 0 && ctx->have_mass, "mass matrix not set");
+    ARG_TRY(ctx, u_dev && w_dev && uhat_dev && c_dev && d_dev && J_host && dist_host, "null argument");
+    ARG_TRY(ctx, K >= 1 && K <= FEMFCT_MAX_TRIALS, "K (number of Armijo trials) must be in 1..16");
+    ARG_TRY(ctx, num_steps >= 1, "num_steps must be >= 1");
+    const int levels = num_steps + 1;
+    LaunchGeom g = femfct_geom(ctx, 1);
+    const int G = g.grid.x;
+    const size_t plen = (size_t)levels * G, plen_m = finaltime ? (size_t)G : plen;
+    int rc = ensure_scratch(ctx, (size_t)K * (plen_m + 2 * plen) + 2 * (size_t)K);
+    if (rc != FEMFCT_OK) return rc;
+    double* pm = ctx->d_scratch;
+    double* pc = pm + (size_t)K * plen_m;
+    double* pd = pc + (size_t)K * plen;
+    double* J = pd + (size_t)K * plen;
+    double* dist = J + K;
+    g.grid.y = (unsigned)(levels < 65535 ? levels : 65535);
+    linear_trials_table(K, std::make_integer_sequence<int, FEMFCT_MAX_TRIALS>())(
+        g.grid, g.block, ctx->stream, ctx->n, ctx->W, ctx->d_cols, ctx->d_M, u_dev, w_dev, uhat_dev, c_dev, d_dev, s0,
+        c_lower, c_upper, levels, finaltime, pm, pc, pd);
+    // the level reductions and scale / accumulate order of femfct_cost_functional and femfct_l2_norm_sq_Q
+    if (!finaltime)
+        hipLaunchKernelGGL(k_reduce_levels, dim3(K), dim3(256), 0, ctx->stream, levels, G, pm, 1, 0.5 * dt, 0, J);
+    else
+        hipLaunchKernelGGL(k_reduce_levels, dim3(K), dim3(256), 0, ctx->stream, 1, G, pm, 0, 0.5, 0, J);
+    hipLaunchKernelGGL(k_reduce_levels, dim3(K), dim3(256), 0, ctx->stream, levels, G, pc, 1, 0.5 * beta * dt, 1, J);
+    hipLaunchKernelGGL(k_reduce_levels, dim3(K), dim3(256), 0, ctx->stream, levels, G, pd, 1, dt, 0, dist);
+    HIP_TRY(ctx, hipMemcpyAsync(J_host, J, sizeof(double) * K, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dist_host, dist, sizeof(double) * K, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return FEMFCT_OK;
+}
+
+int femfct_source_trials(femfct_ctx* ctx, const double* c_dev, const double* d_dev, const double* g_dev, double s0,
+                         int32_t K, double c_lower, double c_upper, int64_t count, double* c_out_dev,
+                         double* src_out_dev) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, c_dev && d_dev && c_out_dev && count >= 0, "bad argument");
+    ARG_TRY(ctx, K >= 1 && K <= FEMFCT_MAX_TRIALS, "K (number of Armijo trials) must be in 1..16");
+    int bs = 256;
+    int64_t gr = (count + bs - 1) / bs;
+    if (gr > 4096) gr = 4096;
+    if (gr < 1) gr = 1;
+    hipLaunchKernelGGL(k_source_trials, dim3((unsigned)gr), dim3(bs), 0, ctx->stream, count, (int)K, c_dev, d_dev, g_dev,
+                       s0, c_lower, c_upper, c_out_dev, src_out_dev);
     return FEMFCT_OK;
 }
 

@@ -365,6 +365,26 @@ class Context:
         check(self.handle, lib.femfct_project_control(self.handle, dptr(c), float(s), dptr(d), float(c_lower),
                                                       float(c_upper), dptr(out), int(count)))
 
+    def linear_trial_costs(self, u, w, uhat, c, d, s0, K, c_lower, c_upper, beta, num_steps, dt, optim):
+        """Costs J[t] = cost_functional(u + s_t w, uhat, c_t) and distances dist[t] = L2_norm_sq_Q(c_t - c) of the K
+        trials s_t = s0 / 2^t, c_t = clip(c + s_t d) of a linear-increment Armijo search, in one fused pass (bitwise the
+        materialised trials).  Returns ``(J, dist)``, two host arrays of K values."""
+        if optim not in ("alltime", "finaltime"):
+            raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+        J, dist = np.empty(max(int(K), 1)), np.empty(max(int(K), 1))
+        check(self.handle, lib.femfct_linear_trial_costs(
+            self.handle, dptr(u), dptr(w), dptr(uhat), dptr(c), dptr(d), float(s0), int(K), float(c_lower),
+            float(c_upper), float(beta), int(num_steps), float(dt), int(optim == "finaltime"), _host_ptr(J),
+            _host_ptr(dist)))
+        return J, dist
+
+    def source_trials(self, c, d, s0, K, c_lower, c_upper, count, c_out, src_out=None, g=None):
+        """c_out[t] = clip(c + s_t d) and src_out[t] = g + c_out[t] (c_out[t] without g) for t < K, one launch; member t
+        starts at t*count."""
+        check(self.handle, lib.femfct_source_trials(self.handle, dptr(c), dptr(d), dptr(g), float(s0), int(K),
+                                                    float(c_lower), float(c_upper), int(count), dptr(c_out),
+                                                    dptr(src_out)))
+
     # -- non-FCT species / PDE systems ---------------------------------------------------
     def descent_pointwise(self, count, beta, c, x, out, y=None, scale=1.0, divisor=1.0):
         """out = -(beta*c - t), t = x*y/divisor (y given) or scale*x"""

@@ -10,6 +10,10 @@ Mirrors the time loops the reference writes in Python around ``FCT_alg[_ref]``
       gradient  advection_solidbody_FCT_PDECO_finaltime.py:228-238
       Armijo    advection_solidbody_FCT_PDECO_finaltime_Garvie.py:259-317
 
+  linear advection-diffusion + distributed source control (pgd_source_control)
+      loop      advection_FCT_PDECO_alltime_exact.py:212-330, advection_FCT_PDECO_finaltime.py:170-280
+      errors    advection_FCT_PDECO_alltime_exact.py:333-440
+
 NumPy-facing methods take/return ``(num_steps+1)*nodes`` float64 arrays in FEniCS
 DoF order, mutate the state array in place *and* return it, like the reference.
 """
@@ -20,7 +24,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .device import Context, DeviceArray
+from .device import Context, DeviceArray, dptr
 from .mesh import SquareMeshP1
 
 
@@ -145,6 +149,15 @@ class LinearSourceControl(SolidBodyDrift):
     def adjoint_state(self, u, uhat, p, optim="alltime", batch=None):
         """:259-274 (all-time) / advection_FCT_PDECO_finaltime.py (final-time)"""
         self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True)
+
+    def descent_direction(self, c, p, beta, d):
+        """advection_FCT_PDECO_alltime_exact.py:278: d = -(beta*c - p), every level, the script's operation order."""
+        self.ctx.descent_pointwise(self.tlen, beta, c, p, d)
+
+    def sensitivity(self, d, w):
+        """:282-297: w = S(d), the state sweep with source d and a zero initial condition (level 0 of ``w`` is zeroed)."""
+        _lib.check(self.ctx.handle, _lib.lib.femfct_memset0(self.ctx.handle, dptr(w), 8 * self.n))
+        self.forward(self._zero_c, w, batch=1, c_shared=True, src=d)
 
     def solve_state(self, src, uk):
         s, u = self.ctx.array(src), self.ctx.array(uk)
@@ -278,3 +291,145 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     finally:
         for a in (u, p, d, c, rhs, c_prev, uh, uhB, cB, uB, ckB):
             a.free()
+
+
+def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
+                       increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both"):
+    """Projected gradient descent for the linear source-control problem, the loop of
+    advection_FCT_PDECO_alltime_exact.py:212-330 (optim="alltime", stop="both") and advection_FCT_PDECO_finaltime.py:
+    170-280 (optim="finaltime", stop="cost"):
+
+        u = S(g + c_k) -> p (all-time: p(T) = 0, load M (uhat_n - u_n); final-time: p(T) = uhat_T - u(T))
+        -> d = -(beta c_k - p) -> Armijo over s_j = s0 / 2^j, c_j = clip(c_k + s_j d): accept the first trial with
+        J_j - J_ref <= -gam / s_j ||c_j - c_k||^2_Q (else the last) -> c_{k+1} = c_j
+
+    increment="linear" (the scripts): J_j = J(u + s_j w, c_j) with the sensitivity w = S(d) (zero IC), all trials in one
+    fused pass (femfct_linear_trial_costs).  increment="resolve" (HEAD's nonlinear_solver branch): J_j = J(S(g + c_j), c_j),
+    the ``max_armijo`` trial states as one batched sweep.  J_ref starts at 10 J(u with level 0 only, c_0), then is the
+    cost the previous iteration accepted.  Stop test: stop_crit = ||c_{k+1} - c_k||^2_Q / ||c_k||^2_Q (infinite while
+    ||c_k|| = 0) and stop_crit2 = |J_ref - J_acc| / |J_ref|; the loop runs while stop_crit2 >= tol, or (stop="both")
+    stop_crit >= tol, and fewer than ``max_iters`` iterations have run.
+
+    ``uhat``: target trajectory (all-time) or uhat_T (final-time, n values); ``g``: fixed source trajectory or None.
+    Everything stays in HBM; the host sees scalars only.  Returns ``(u, p, c, hist)`` like the scripts: u and p are the
+    last iteration's state and adjoint (at the control that iteration started from), c the last accepted control.
+    hist["cost"][k] is the accepted J_acc (the linear estimate in linear mode); hist["cost_state"][k] the cost
+    J(S(g + c_k), c_k) of the re-solved state at the control iteration k started from, so hist["cost_state"][k + 1]
+    re-solves hist["cost"][k]."""
+    if optim not in ("alltime", "finaltime"):
+        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+    if increment not in ("linear", "resolve"):
+        raise ValueError(f"Invalid value for 'increment': '{increment}'. Must be one of ['linear', 'resolve'].")
+    if stop not in ("both", "cost"):
+        raise ValueError(f"Invalid value for 'stop': '{stop}'. Must be one of ['both', 'cost'].")
+    K = int(max_armijo)
+    if not 1 <= K <= _lib.MAX_TRIALS:
+        raise ValueError(f"max_armijo = {K}: must be in 1..{_lib.MAX_TRIALS}")
+    alltime, linear = optim == "alltime", increment == "linear"
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    uhat = np.asarray(uhat, dtype=np.float64).ravel()
+    if uhat.size != (tl if alltime else n):
+        raise ValueError(f"target of {uhat.size} values, expected {tl if alltime else n} for optim='{optim}'")
+    c0 = np.asarray(c0, dtype=np.float64).ravel()
+    if c0.size != tl:
+        raise ValueError(f"c0 of {c0.size} values, expected {tl}")
+    if g is not None and np.asarray(g).size != tl:
+        raise ValueError(f"g of {np.asarray(g).size} values, expected {tl}")
+    u0 = np.asarray(u0, dtype=np.float64).ravel()
+    if u0.size != n:
+        raise ValueError(f"u0 of {u0.size} values, expected {n}")
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    try:
+        u, p, d, c = alloc(tl), alloc(tl), alloc(tl), alloc(tl, False).upload(c0)
+        u.upload(np.concatenate([u0, np.zeros(tl - n)]))
+        uh = alloc(uhat.size, False).upload(uhat)
+        gd = None if g is None else alloc(tl, False).upload(g)
+        src = c if gd is None else alloc(tl, False)
+        if linear:
+            w = alloc(tl)
+        else:
+            cB, uB, ckB, uhB = alloc(K * tl, False), alloc(K * tl), alloc(K * tl, False), alloc(K * uhat.size, False)
+            srcB = cB if gd is None else alloc(K * tl, False)
+            for k in range(K):
+                uB.copy_from(u, n, dst_off=k * tl)              # level 0 of every trial state = u0
+                uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
+        cost = lambda uu, cc: float(prob.cost(uu, uh, cc, beta, optim, batch=1)[0])
+        J_ref = 10 * cost(u, c)                                 # alltime_exact.py:212 / finaltime.py:170
+        hist = dict(cost=[], cost_state=[], armijo_k=[], step=[], stop_crit=[], stop_crit2=[], armijo_margin=[],
+                    wall=[], wall0=time.perf_counter())
+        svals = [s0 * (1 / 2 ** k) for k in range(K)]
+        stop1 = stop2 = np.inf
+        while ((stop2 >= tol) or (stop == "both" and stop1 >= tol)) and len(hist["cost"]) < max_iters:
+            if gd is not None:
+                ctx.axpby(tl, 1.0, gd, 1.0, c, src)
+            prob.state(src, u, batch=1)
+            hist["cost_state"].append(cost(u, c))
+            prob.adjoint_state(u, uh, p, optim, batch=1)
+            prob.descent_direction(c, p, beta, d)
+            if linear:
+                prob.sensitivity(d, w)
+                J, dist = ctx.linear_trial_costs(u, w, uh, c, d, s0, K, c_lower, c_upper, beta, Nt, dt, optim)
+            else:
+                ctx.source_trials(c, d, s0, K, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
+                prob.state(srcB, uB, batch=K)
+                J = prob.cost(uB, uhB, cB, beta, optim, batch=K)
+                for k in range(K):
+                    ckB.copy_from(c, tl, dst_off=k * tl)
+                dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=K)
+            margins = []
+            for k, s in enumerate(svals):
+                acc = k
+                margins.append((float(J[k]) - J_ref + gam / s * float(dist[k])) / abs(J_ref))
+                if J[k] - J_ref <= -gam / s * dist[k]:
+                    break
+            J_acc, dist_acc = float(J[acc]), float(dist[acc])
+            nc = float(ctx.l2_norm_sq_Q(c, None, Nt, dt)[0])
+            stop1 = dist_acc / nc if nc > 0 else np.inf
+            stop2 = abs(J_ref - J_acc) / abs(J_ref)
+            if linear:
+                ctx.project_control(c, svals[acc], d, c_lower, c_upper, c, tl)     # = the fused kernel's c_acc, bitwise
+            else:
+                c.copy_from(cB, tl, src_off=acc * tl)
+            for key, v in (("cost", J_acc), ("armijo_k", acc + 1), ("step", svals[acc]), ("stop_crit", stop1),
+                           ("stop_crit2", stop2), ("armijo_margin", margins), ("wall", time.perf_counter())):
+                hist[key].append(v)
+            J_ref = J_acc
+        hist["iterations"] = len(hist["cost"])
+        hist["armijo_margin_min"] = min((abs(m) for ms in hist["armijo_margin"] for m in ms), default=None)
+        return u.download(), p.download(), c.download(), hist
+    finally:
+        for a in bufs:
+            a.free()
+
+
+def source_control_errors(mesh: SquareMeshP1, u, c, p, exact, dx, dt, iterations=0):
+    """The error table of advection_FCT_PDECO_alltime_exact.py:333-440 (host NumPy).  ``exact(t)`` returns a dict with
+    the manufactured fields "u", "c", "p" at time t in vertex order.  Per level i < num_steps, u is compared at level
+    i + 1 and c, p at level i (the adjoint and control are one step behind), each in vertex order: the Euclidean error,
+    relative to the exact field and weighted by dx.  Returns the maxima over the levels, ``iterations`` and the script's
+    CSV line (:440)."""
+    v2d = mesh.vertex_to_dof
+    n = v2d.size
+    lv = lambda a, i: np.asarray(a, dtype=np.float64)[i * n:(i + 1) * n][v2d]      # level i, vertex order
+    num_steps = np.asarray(u).size // n - 1
+    E = {k: [] for k in ("u", "c", "p")}
+    R = {k: [] for k in ("u", "c", "p")}
+    for i in range(num_steps):
+        exU, exP = exact((i + 1) * dt), exact(i * dt)
+        for key, comp, ex in (("u", lv(u, i + 1), exU["u"]), ("c", lv(c, i), exP["c"]), ("p", lv(p, i), exP["p"])):
+            ex = np.asarray(ex, dtype=np.float64).reshape(n)
+            e = np.linalg.norm(ex - comp)
+            E[key].append(e)
+            R[key].append(e / np.linalg.norm(ex))
+    out = {f"rel_{k}": max(R[k]) for k in R}
+    out.update({f"werr_{k}": dx * max(E[k]) for k in E})
+    out["iterations"] = int(iterations)
+    vals = [out["rel_u"], out["rel_c"], out["rel_p"], out["werr_u"], out["werr_c"], out["werr_p"]]
+    out["csv"] = " , ".join(str(float(v)) for v in vals) + f" , {int(iterations)}"
+    return out

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct, femfct_nonlinear_adjoint_alltime (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
+#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct, femfct_nonlinear_adjoint_alltime, femfct_linear_trial_costs, femfct_source_trials (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
 
 typedef struct femfct_ctx femfct_ctx;
 
@@ -267,6 +267,23 @@ int femfct_cost_functional(femfct_ctx* ctx, const double* var1, const double* va
 /* update_control: out = clip(c + s*d, c_lower, c_upper)  helpers.py:1666-1667 (out may alias c) */
 int femfct_project_control(femfct_ctx* ctx, const double* c_dev, double s, const double* d_dev,
                            double c_lower, double c_upper, double* out_dev, int64_t count);
+
+/* Armijo trial batches of the linear source-control PDECO (advection_FCT_PDECO_{alltime_exact,finaltime}.py, helpers.py:
+ * 1681-1708): trial t < K has s_t = s0 * (1 / 2^t) and c_t = clip(c + s_t d, c_lower, c_upper). */
+#define FEMFCT_MAX_TRIALS 16
+/* Linear increment: J_host[t] = cost_functional(u + s_t w, uhat, c_t, ...) and dist_host[t] = L2_norm_sq_Q(c_t - c), all K
+ * trials in one pass over the five trajectories (one trajectory each, (num_steps+1)*n doubles; uhat is n doubles when
+ * finaltime).  Bitwise equal to materialising each trial (femfct_project_control, femfct_axpby(1, u, s_t, w)) and calling
+ * femfct_cost_functional and femfct_l2_norm_sq_Q.  Synchronises. */
+int femfct_linear_trial_costs(femfct_ctx* ctx, const double* u_dev, const double* w_dev, const double* uhat_dev,
+                              const double* c_dev, const double* d_dev, double s0, int32_t K, double c_lower,
+                              double c_upper, double beta, int32_t num_steps, double dt, int32_t finaltime,
+                              double* J_host, double* dist_host);
+/* Resolve mode: c_out[t*count ..] = c_t and src_out[t*count ..] = g + c_t (g NULL: c_t; src_out may be NULL), the
+ * expressions of femfct_project_control and femfct_axpby(1, g, 1, c_t), in one launch. */
+int femfct_source_trials(femfct_ctx* ctx, const double* c_dev, const double* d_dev, const double* g_dev, double s0,
+                         int32_t K, double c_lower, double c_upper, int64_t count, double* c_out_dev,
+                         double* src_out_dev);
 
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
