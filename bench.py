@@ -19,7 +19,12 @@ N > 1: every rank runs the same sweep for its own regularisation value beta (con
 embarrassingly parallel) and the ranks all-gather their cost values over RCCL once per step;
 "scaling": "weak".
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line (value,
+ms_per_step, cost, config).  Everything else the benchmark measures or checks runs only with --full, after the timed
+steps: per-kernel timing at C2 size (kernels_c2), roofline, batched, systems, small_mesh_batches, pgd_c2,
+pgd_c5_mixed_decisions, cpu_baseline, parity, tolerance_table; for N > 1 the sweep's cpu_baseline.
+
+Extra objects in the JSON line of a --full run, among them:
   roofline      HBM roofline of the dominant kernel on a large synthetic mesh (n = 2049^2: the C2
                 working set is cache resident), timed live with HIP events on the library's stream.
                 `achieved`/`frac` price the COMPULSORY bytes of a launch as executed (every array the
@@ -461,6 +466,10 @@ def main():
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1, help="independent trajectories per launch on each GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every sub-benchmark and check as well (per-kernel timing, roofline, "
+                         "batched, systems, PGD loops, CPU baseline, parity, tolerance table); --roofline-cells, --roofline-steps, "
+                         "--cpu-sample, --pgd-iters, --batched, --tolerance-table and --systems select among them")
     ap.add_argument("--roofline-cells", type=int, default=2048, help="cells per side of the roofline mesh (0: skip)")
     ap.add_argument("--roofline-steps", type=int, default=3)
     ap.add_argument("--cpu-sample", type=int, default=250,
@@ -627,6 +636,11 @@ def main():
                              "solver_resid_max": float(log["solver_resid"].max()), "graphs": True,
                              "graph_replay": bool(ctx.graph_replay_active()),   # False under rocprofv3
                              "kernel_regime": int(ctx.kernel_regime(B)), "source_sha16": source_sha16()})
+    if not args.full:             # a plain run ends with the headline line: everything below is --full
+        ranks.close()
+        if rank == 0:
+            emit(result)
+        return
 
     # ---------------------------------------------------- per-kernel timing at C2 size
     if rank == 0:

@@ -72,3 +72,19 @@ def test_bench_dump_outputs_are_the_timed_paths_and_repeat(tmp_path):
     for k in o2:
         assert np.isfinite(o2[k]).all()
         np.testing.assert_allclose(o3[k], o2[k], rtol=1e-12, atol=1e-14, err_msg=k)   # same inputs, same outputs
+
+
+@pytest.mark.gpu
+def test_plain_bench_prints_the_headline_and_full_adds_the_sub_benchmarks():
+    extras = {"kernels_c2", "roofline", "batched", "systems", "small_mesh_batches", "pgd_c2", "pgd_c5_mixed_decisions",
+              "cpu_baseline", "parity", "tolerance_table"}
+    plain = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1"], 300)
+    assert plain["steps"] == 2 and plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["cost"] > 0
+    assert plain["metric"] == "FCT timesteps/sec (fwd+adj)" and plain["unit"] == "timesteps/s" and plain["dtype"] == "f64"
+    assert plain["higher_is_better"] is True and len(plain["config"]["source_sha16"]) == 16
+    assert not extras & set(plain), sorted(extras & set(plain))
+    full = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--roofline-cells", "0", "--cpu-sample", "0",
+                       "--pgd-iters", "0", "--batched=", "--systems", "0"], 300)
+    assert full["kernels_c2"] and all(e["launches_per_sweep"] > 0 for e in full["kernels_c2"].values())
+    assert not (extras - {"kernels_c2"}) & set(full)                      # the others were switched off one by one
+    assert abs(full["cost"] - plain["cost"]) <= 1e-12 * plain["cost"]    # same inputs, same timed path

@@ -48,7 +48,7 @@ def test_bench_two_ranks_real_solver_on_one_gpu_gloo():
     root = os.path.dirname(EX)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--backend", "gloo", "--roofline-cells", "0"], capture_output=True, text=True, timeout=400, env=env)
+                          "--backend", "gloo", "--roofline-cells", "0", "--full"], capture_output=True, text=True, timeout=400, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

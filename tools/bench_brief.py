@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Run bench.py with the given arguments and print a one-line summary (tuning helper)."""
+"""Run bench.py --full with the given arguments and print a one-line summary (tuning helper)."""
 import json
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + sys.argv[1:], capture_output=True, text=True)
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + sys.argv[1:], capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not line:
     print(out.stdout[-2000:], out.stderr[-4000:])

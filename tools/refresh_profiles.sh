@@ -4,7 +4,7 @@
 #   gpurun --timeout 1190 -- 'bash tools/refresh_profiles.sh r04'
 # Outputs land in gpurun_out/prof/ (merged back by gpurun); copy them into profiles/ with
 #   cp gpurun_out/prof/r04_* gpurun_out/prof/traffic.json profiles/
-# Order: PMC passes first (traffic.json, stamped with source_sha16), then the plain bench run (whose
+# Order: PMC passes first (traffic.json, stamped with source_sha16), then the --full bench run (whose
 # roofline.traffic echoes that stamp-checked file), then the kernel trace.
 set -e
 TAG=${1:-r04}
@@ -13,7 +13,7 @@ OUT=$REPO/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 N_ROOF=4198401          # 2049^2, the roofline mesh of bench.py
-PMC_ARGS="--cpu-sample 0 --pgd-iters 0 --batched= --steps 1 --warmup 1 --systems 0 --tolerance-table 0"
+PMC_ARGS="--full --cpu-sample 0 --pgd-iters 0 --batched= --steps 1 --warmup 1 --systems 0 --tolerance-table 0"
 echo "[refresh] PMC FETCH_SIZE pass"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pf -- python3 $REPO/bench.py $PMC_ARGS > /dev/null 2> $OUT/pf.err
 echo "[refresh] PMC WRITE_SIZE pass"
@@ -32,13 +32,13 @@ python3 $REPO/tools/pmc_traffic.py $OUT/fetch2.csv $OUT/write2.csv $N_ROOF2 $OUT
 cp $OUT/traffic.json $REPO/profiles/traffic.json      # on the box: the bench runs below read it
 echo "[refresh] bench run"
 cd $REPO
-timeout -k 10 400 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 echo "[refresh] kernel trace"
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $REPO/bench.py --cpu-sample 0 --batched= --systems 0 --tolerance-table 0 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/kt.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $REPO/bench.py --full --cpu-sample 0 --batched= --systems 0 --tolerance-table 0 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/kt.err
 cp $(find $OUT/kt -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 echo "[refresh] kernel trace of the BATCHED regime (64 C2 trajectories per launch: the lever at the config sizes)"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kb -- python3 $REPO/bench.py --batch 64 --steps 3 --warmup 1 --roofline-cells 0 --cpu-sample 0 --pgd-iters 0 --batched= --systems 0 --tolerance-table 0 > $OUT/${TAG}_bench_batch64_under_rocprof.json 2> $OUT/kb.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kb -- python3 $REPO/bench.py --full --batch 64 --steps 3 --warmup 1 --roofline-cells 0 --cpu-sample 0 --pgd-iters 0 --batched= --systems 0 --tolerance-table 0 > $OUT/${TAG}_bench_batch64_under_rocprof.json 2> $OUT/kb.err
 cp $(find $OUT/kb -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_bench_batch64_kernel_stats.csv
 echo "[refresh] the other systems' sweeps under the same profiler command that used to fault (DESIGN.md section 9)"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -- python3 $REPO/tools/bench_systems.py > $OUT/${TAG}_systems_under_rocprof.txt 2>&1 && echo "exit code 0" >> $OUT/${TAG}_systems_under_rocprof.txt || echo "exit code $? (non-zero)" >> $OUT/${TAG}_systems_under_rocprof.txt
@@ -50,6 +50,6 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k
 cp $(find $OUT/km -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_mesh41_kernel_stats.csv
 echo "[refresh] roofline entry at 4097 x 4097"
 cd $REPO
-timeout -k 10 400 python3 bench.py --roofline-cells 4096 --steps 2 --warmup 1 --cpu-sample 0 --pgd-iters 0 --batched= --systems 0 --tolerance-table 0 > $OUT/${TAG}_bench_roofline4097.json 2> $OUT/b4097.err
+timeout -k 10 400 python3 bench.py --full --roofline-cells 4096 --steps 2 --warmup 1 --cpu-sample 0 --pgd-iters 0 --batched= --systems 0 --tolerance-table 0 > $OUT/${TAG}_bench_roofline4097.json 2> $OUT/b4097.err
 rm -rf $OUT/kt $OUT/kb $OUT/ks $OUT/km $OUT/pf $OUT/pw $OUT/pf2 $OUT/pw2 $OUT/fetch.csv $OUT/write.csv $OUT/fetch2.csv $OUT/write2.csv
 ls -la $OUT
