@@ -163,12 +163,14 @@ def test_chemotaxis_forward_adjoint_vs_oracle(hp, optim):
         hp.solve_adjoint_chtxs_system(ug, vg, uhat, vhat, pg, qg, ctrl, Nt * dt, V, n, Nt, dt, None, "sometime")
 
 
-def test_species_chebyshev_matches_bicgstab(hp):
-    """The tile-fused Chebyshev species solve (vertex order) and BiCGStab meet the same tolerance:
-    identical Schnakenberg / chemotaxis trajectories to solver accuracy; the flag tells which ran."""
+@pytest.mark.parametrize("nc", [40, 60])
+def test_species_chebyshev_matches_bicgstab(hp, nc):
+    """The Chebyshev species solve (vertex order) and BiCGStab meet the same tolerance: identical Schnakenberg /
+    chemotaxis trajectories to solver accuracy; the flag tells which ran.  At nc = 40 (n = 1681 <= 2048) the Chebyshev
+    solve is the one-workgroup mesh solve (k_mesh_cheb_solve), at nc = 60 the tile-fused one on 32-patch tiles."""
     import os
     systems = importlib.import_module("fem-fct-pdeco_amd.systems")
-    V = hp.SquareMeshP1(0.0, 1.0, 40)
+    V = hp.SquareMeshP1(0.0, 1.0, nc)
     n, Nt, dt = V.nodes, 12, 5e-4
     rng = np.random.default_rng(11)
     # the Chebyshev variant needs the tile kernels (tuning knobs may switch them off: then BiCGStab runs)
@@ -178,7 +180,7 @@ def test_species_chebyshev_matches_bicgstab(hp):
     try:
         par, wind = systems._schnak_par()
         Aw, AwT = S.convection(wind, "schnak")
-        u0, v0 = hp.schnak_sys_IC(0, 1, 0.025, n, np.arange(n))
+        u0, v0 = hp.schnak_sys_IC(0, 1, 1 / nc, n, np.arange(n))
         c = ctx.array(0.1 + 0.01 * rng.random(n))
         cpar = systems._chtxs_par()
         cc = ctx.array(20 * rng.random(n))
