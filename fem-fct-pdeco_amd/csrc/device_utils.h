@@ -94,8 +94,13 @@ __device__ __forceinline__ RowRange block_rows(int n) {
 // Reductions (wave64 shuffles, then LDS across the block's waves).  All of them
 // return the result in every thread.  smem must hold >= 32 doubles.
 // ---------------------------------------------------------------------------
-struct OpMax { __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); } };
-struct OpMin { __device__ __forceinline__ double operator()(double a, double b) const { return fmin(a, b); } };
+// max / min that carry a NaN operand, where fmax / fmin drop it: every residual maximum, ||b|| and minimal row sum goes
+// through them, so that a NaN anywhere fails the solve's test (written !(r <= tol)) instead of vanishing from it.  On
+// operands without a NaN they are fmax / fmin (the same bits).
+__device__ __forceinline__ double nan_max(double a, double b) { return __builtin_isunordered(a, b) ? a + b : fmax(a, b); }
+__device__ __forceinline__ double nan_min(double a, double b) { return __builtin_isunordered(a, b) ? a + b : fmin(a, b); }
+struct OpMax { __device__ __forceinline__ double operator()(double a, double b) const { return nan_max(a, b); } };
+struct OpMin { __device__ __forceinline__ double operator()(double a, double b) const { return nan_min(a, b); } };
 struct OpSum { __device__ __forceinline__ double operator()(double a, double b) const { return a + b; } };
 
 template <class Op>
@@ -127,8 +132,20 @@ __device__ __forceinline__ double wave_reduce_dpp(double v, Op op) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double wave_reduce(double v, OpMax op) { return wave_reduce_dpp(v, op); }
-__device__ __forceinline__ double wave_reduce(double v, OpMin op) { return wave_reduce_dpp(v, op); }
+// NaN-carrying over the wave: the tree runs on plain fmax / fmin and one ballot adds the NaN of any lane (a NaN-carrying
+// op at each of the six steps costs the sweep kernels, which reduce once per sweep, several percent)
+struct FMax { __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); } };
+struct FMin { __device__ __forceinline__ double operator()(double a, double b) const { return fmin(a, b); } };
+__device__ __forceinline__ double wave_reduce(double v, OpMax) {
+    const bool nan = __any(v != v);
+    const double r = wave_reduce_dpp(v, FMax());
+    return nan ? (double)NAN : r;
+}
+__device__ __forceinline__ double wave_reduce(double v, OpMin) {
+    const bool nan = __any(v != v);
+    const double r = wave_reduce_dpp(v, FMin());
+    return nan ? (double)NAN : r;
+}
 
 // the same tree for sums (lanes without a source add 0): a fixed order, so still deterministic
 template <int CTRL, int ROW_MASK>
@@ -149,6 +166,11 @@ __device__ __forceinline__ double wave_reduce(double v, OpSum) {
     return __hiloint2double(hi, lo);
 }
 
+// the fold of the per-wave results: plain fmax / fmin on the serial chain, the NaN test of each value beside it
+__device__ __forceinline__ double fold_plain(double a, double b, OpMax) { return fmax(a, b); }
+__device__ __forceinline__ double fold_plain(double a, double b, OpMin) { return fmin(a, b); }
+__device__ __forceinline__ double fold_plain(double a, double b, OpSum) { return a + b; }
+
 template <class Op>
 __device__ __forceinline__ double block_reduce(double v, Op op, double identity, double* smem) {
     v = wave_reduce(v, op);
@@ -159,8 +181,13 @@ __device__ __forceinline__ double block_reduce(double v, Op op, double identity,
     if (lane == 0) smem[wid] = v;
     __syncthreads();
     double r = identity;
-    for (int w = 0; w < nw; ++w) r = op(r, smem[w]);  // fixed order: deterministic
-    return r;
+    bool nan = false;
+    for (int w = 0; w < nw; ++w) {  // fixed order: deterministic
+        const double x = smem[w];
+        r = fold_plain(r, x, op);
+        nan = nan || x != x;
+    }
+    return nan ? (double)NAN : r;
 }
 
 // Three reductions (max, max, min) with one barrier pair instead of three; smem must hold >= 96 doubles.
@@ -175,10 +202,13 @@ __device__ __forceinline__ void block_reduce_max_max_min(double& a, double& b, d
     if (lane == 0) { smem[wid] = a; smem[32 + wid] = b; smem[64 + wid] = c; }
     __syncthreads();
     double ra = 0.0, rb = 0.0, rc = INFINITY;
+    bool na = false, nb = false, nc = false;
     for (int w = 0; w < nw; ++w) {   // fixed order: deterministic
-        ra = fmax(ra, smem[w]); rb = fmax(rb, smem[32 + w]); rc = fmin(rc, smem[64 + w]);
+        const double xa = smem[w], xb = smem[32 + w], xc = smem[64 + w];
+        ra = fmax(ra, xa); rb = fmax(rb, xb); rc = fmin(rc, xc);
+        na = na || xa != xa; nb = nb || xb != xb; nc = nc || xc != xc;
     }
-    a = ra; b = rb; c = rc;
+    a = na ? (double)NAN : ra; b = nb ? (double)NAN : rb; c = nc ? (double)NAN : rc;
 }
 
 // Every block reduces the same `count` per-block partials in the same order, so

@@ -55,8 +55,8 @@ __global__ void k_kry_init(int n, int W, const int32_t* __restrict__ cols, const
         double ri = bi - acc;
         x[i] = xi; r[i] = ri; rh[i] = ri; p0[i] = 0.0; v0[i] = 0.0;
         rho += ri * ri;
-        rmax = fmax(rmax, fabs(ri));
-        bmax = fmax(bmax, fabs(bi));
+        rmax = nan_max(rmax, fabs(ri));
+        bmax = nan_max(bmax, fabs(bi));
     }
     rho = block_reduce(rho, OpSum(), 0.0, smem);
     rmax = block_reduce(rmax, OpMax(), 0.0, smem);
@@ -82,7 +82,7 @@ __global__ void k_kry_a(int n, int W, const int32_t* __restrict__ cols, const do
     double rho_new = reduce_partials(KP(part, 0), G, OpSum(), 0.0, smem);
     if (rmax <= rel_tol * bnorm) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            ctl->done = 1; ctl->iters = it; ctl->resid = bnorm > 0.0 ? rmax / bnorm : 0.0; ctl->bnorm = bnorm;
+            ctl->done = 1; ctl->iters = it; ctl->resid = bnorm != 0.0 ? rmax / bnorm : 0.0; ctl->bnorm = bnorm;
         }
         return;
     }
@@ -183,7 +183,7 @@ __global__ void k_kry_c(int n, int W, const double* __restrict__ A_, int ashared
         double ri = si - omega * tv[i];
         r[i] = ri;
         rho += rh[i] * ri;
-        rmax = fmax(rmax, fabs(ri));
+        rmax = nan_max(rmax, fabs(ri));
     }
     rho = block_reduce(rho, OpSum(), 0.0, smem);
     rmax = block_reduce(rmax, OpMax(), 0.0, smem);
@@ -201,7 +201,7 @@ __global__ void k_kry_finish(int n, KryVecs kv, VecRef out_ref, int64_t out_bs, 
         double rmax = reduce_partials(KP(part, 4), gridDim.x, OpMax(), 0.0, smem);
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             double bn = ctl->bnorm;
-            ctl->resid = bn > 0.0 ? rmax / bn : 0.0;
+            ctl->resid = bn != 0.0 ? rmax / bn : 0.0;
             if (!(rmax <= rel_tol * bn)) ctl->flags |= FEMFCT_FLAG_SOLVER_BUDGET;
         }
     }
@@ -374,8 +374,8 @@ __global__ void k_chs_check(int n, int W, const int32_t* __restrict__ cols, cons
         const double bi = b[i];
         const double ri = fabs(bi - acc);
         rmax = (ri == ri) ? fmax(rmax, ri) : INFINITY;
-        bmax = fmax(bmax, fabs(bi));
-        amax = fmax(amax, aabs);
+        bmax = nan_max(bmax, fabs(bi));
+        amax = nan_max(amax, aabs);
     }
     rmax = block_reduce(rmax, OpMax(), 0.0, smem);
     bmax = block_reduce(bmax, OpMax(), 0.0, smem);
@@ -403,8 +403,8 @@ __global__ void k_chs_finish(const double* __restrict__ part_, int G, KrylovCtl*
     const double amax = reduce_partials(KP(part, 3), G, OpMax(), 0.0, smem);
     if (threadIdx.x == 0) {
         KrylovCtl* c = ctl_ + bz;
-        const double scale = rel_tol > 0.0 ? fmax(bmax, CHS_FLOOR * DBL_EPSILON * amax / rel_tol) : bmax;
-        const double res = scale > 0.0 ? rmax / scale : (rmax > 0.0 ? INFINITY : 0.0);
+        const double scale = rel_tol > 0.0 ? nan_max(bmax, CHS_FLOOR * DBL_EPSILON * amax / rel_tol) : bmax;
+        const double res = scale != 0.0 ? rmax / scale : (rmax == 0.0 ? 0.0 : INFINITY);
         c->resid = res;
         c->bnorm = bmax;
         c->done = 1;
@@ -495,7 +495,7 @@ k_mesh_cheb_solve(int n, int Wrt, const int32_t* __restrict__ cols, const double
     double mn = INFINITY, bmax = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         mn = fmin(mn, (tau >= 0.0 ? Mdiag[i] + tau * Kdiag[i] : Mdiag[i]) / A[i]);
-        bmax = fmax(bmax, fabs(b[i]));
+        bmax = nan_max(bmax, fabs(b[i]));
     }
     mn = block_reduce(mn, OpMin(), INFINITY, smem);
     bmax = block_reduce(bmax, OpMax(), 0.0, smem);
@@ -544,7 +544,7 @@ k_mesh_cheb_solve(int n, int Wrt, const int32_t* __restrict__ cols, const double
             double z = fma(-inv_scale, ym[q], bs[q]);
 #pragma unroll
             for (int s = 0; s < W - 1; ++s) z = fma(-ms[q][s], y_mid[nb[q][s]], z);
-            zmax = fmax(zmax, fabs(z) * sa[q]);                 // |r_i| of the current iterate
+            zmax = nan_max(zmax, fabs(z) * sa[q]);                 // |r_i| of the current iterate
             yn[q] = omega * (z + ym[q] - yo[q]) + yo[q];
         }
         if ((k % CHECK) == 0) {                                  // uniform decision: everybody reduces the same value
@@ -568,7 +568,7 @@ k_mesh_cheb_solve(int n, int Wrt, const int32_t* __restrict__ cols, const double
             double z = fma(-inv_scale, ym[q], bs[q]);
 #pragma unroll
             for (int s = 0; s < W - 1; ++s) z = fma(-ms[q][s], y_mid[nb[q][s]], z);
-            zmax = fmax(zmax, fabs(z) * sa[q]);
+            zmax = nan_max(zmax, fabs(z) * sa[q]);
         }
         res = block_reduce(zmax, OpMax(), 0.0, smem);
     }
@@ -577,7 +577,7 @@ k_mesh_cheb_solve(int n, int Wrt, const int32_t* __restrict__ cols, const double
         if (idx[q] >= 0) out[idx[q]] = ym[q];
     if (threadIdx.x == 0) {
         KrylovCtl* c = ctl_ + bz;
-        const double rr = bmax > 0.0 ? res / bmax : (res > 0.0 ? INFINITY : 0.0);
+        const double rr = bmax != 0.0 ? res / bmax : (res == 0.0 ? 0.0 : INFINITY);
         c->flags = FEMFCT_FLAG_CHEBYSHEV;
         c->done = 1;
         c->resid = rr;

@@ -193,7 +193,7 @@ __device__ __forceinline__ void reduce4(double& a, double& b, double& c, double&
     __syncthreads();
     double ra = 0.0, rb = INFINITY, rc = 0.0, rd = 0.0;
     MS_UNROLL for (int w = 0; w < NW; ++w) {
-        ra = fmax(ra, red[w]); rb = fmin(rb, red[NW + w]); rc = fmax(rc, red[2 * NW + w]); rd = fmax(rd, red[3 * NW + w]);
+        ra = nan_max(ra, red[w]); rb = nan_min(rb, red[NW + w]); rc = nan_max(rc, red[2 * NW + w]); rd = nan_max(rd, red[3 * NW + w]);
     }
     a = uniform(ra); b = uniform(rb); c = uniform(rc); d = uniform(rd);
 }
@@ -356,12 +356,12 @@ __device__ __forceinline__ void mesh_step_body(const MeshStepArgs& a, double* ld
                 const double ld = mli + dt * (a0 + dsv[c]) + vz(r, c, dt * nmv[c]);
                 if (HASNM) nrow[r][c] += nmv[c];
                 const double bi = mli * ui + vz(r, c, dt * rb[c]);
-                bmax = fmax(bmax, fabs(bi));
+                bmax = nan_max(bmax, fabs(bi));
                 const double rinv = frcp(ld);
                 MS_UNROLL for (int q = 0; q < 6; ++q) lc[q][r][c] *= rinv;
                 if (LEAN) {
                     *dst(r, c, 2 * IMG) = bi * rinv;
-                    ldmax = fmax(ldmax, ld);
+                    ldmax = nan_max(ldmax, ld);
                 } else {
                     bp[r][c] = bi * rinv;
                     ldv[r][c] = ld;
@@ -450,13 +450,13 @@ __device__ __forceinline__ void mesh_step_body(const MeshStepArgs& a, double* ld
                     acc = fma(-lc[2][r][c], nb(1, 0), acc);
                     acc = fma(-lc[5][r][c], nb(-1, 0), acc);
                     acc = vz(r, c, acc);
-                    rmx = fmax(rmx, LEAN ? fabs(acc - x[r][c]) : fabs(acc - x[r][c]) * ldv[r][c]);
+                    rmx = nan_max(rmx, LEAN ? fabs(acc - x[r][c]) : fabs(acc - x[r][c]) * ldv[r][c]);
                     x[r][c] = acc;
                 }
                 MS_FENCE();
             }
             publish_rim<BX, BY>(x, img_out, dst);
-            const bool viol = rmx > tolb;
+            const bool viol = !(rmx <= tolb);                 // (a NaN violates)
             if (__any(viol) && (threadIdx.x % WAVE) == 0) flg[k % 3] = 1;
             if (threadIdx.x == 0) flg[(k + 1) % 3] = 0;
             __syncthreads();
@@ -511,7 +511,7 @@ __device__ __forceinline__ void mesh_step_body(const MeshStepArgs& a, double* ld
                     {
                         const double mlr = INTERIOR ? hh : 2.0 * mdv[c];      // M_L = 2 m_ii on this mesh
                         const double rs = mlr + dt * (asum + nsum[c]);
-                        rsmin = valid(r, c) ? fmin(rsmin, rs) : rsmin;
+                        rsmin = valid(r, c) ? nan_min(rsmin, rs) : rsmin;
                     }
                     double rr = -acc + rd[c];
                     if (INTERIOR) {
@@ -537,7 +537,7 @@ __device__ __forceinline__ void mesh_step_body(const MeshStepArgs& a, double* ld
         {
             double r0 = rmx, r2 = 0.0, r3 = 0.0;
             reduce4<NW>(r0, rsmin, r2, r3, red);
-            resid = bmax > 0.0 ? (LEAN ? r0 * ldmax : r0) / bmax : 0.0;      // (LEAN: the bound the test went by)
+            resid = bmax != 0.0 ? (LEAN ? r0 * ldmax : r0) / bmax : 0.0;      // (LEAN: the bound the test went by)
             if (!(rsmin > 0.0)) sflags |= FEMFCT_FLAG_MMATRIX_ROWSUM;
         }
         publish_rim<BX, BY>(x, 2 * IMG, dst);

@@ -216,8 +216,8 @@ __device__ __forceinline__ void build_low_body(int n, int Wrt, int Nw, const int
         double bi = mli * ui + (rhs ? dt * rhs[i] : 0.0);
         b[i] = bi;
         x0[i] = ui;
-        bmax = fmax(bmax, fabs(bi));
-        rsmin = fmin(rsmin, rs);
+        bmax = nan_max(bmax, fabs(bi));
+        rsmin = nan_min(rsmin, rs);
     }
     bmax = block_reduce(bmax, OpMax(), 0.0, smem);
     rsmin = block_reduce(rsmin, OpMin(), INFINITY, smem);
@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(BS) k_jacobi(int n, int Wrt, int Nw, const int
         if (rmax <= rel_tol * bnorm) {
             if (blockIdx.x == 0 && threadIdx.x == 0) {
                 ctl->done = 1; ctl->parity = sweep & 1; ctl->iters = sweep;
-                ctl->resid = bnorm > 0.0 ? rmax / bnorm : 0.0;
+                ctl->resid = bnorm != 0.0 ? rmax / bnorm : 0.0;
             }
             return;
         }
@@ -312,7 +312,7 @@ __global__ void __launch_bounds__(BS) k_jacobi(int n, int Wrt, int Nw, const int
         double xi = xin[i];
         double xn = acc / ld;
         xout[i] = xn;
-        rmax = fmax(rmax, fabs(acc - ld * xi));   // |r_i(x_in)|
+        rmax = nan_max(rmax, fabs(acc - ld * xi));   // |r_i(x_in)|
     }
     rmax = block_reduce(rmax, OpMax(), 0.0, smem);
     if (threadIdx.x == 0) p[(sweep & 1) * FEMFCT_MAX_PARTIALS + blockIdx.x] = rmax;

@@ -52,7 +52,7 @@ k_strip_jacobi(int n, const int32_t* __restrict__ cols, const double* __restrict
         if (rmax <= rel_tol * bnorm) {
             if (blockIdx.x == 0 && threadIdx.x == 0) {
                 ctl->done = 1; ctl->parity = launch & 1; ctl->iters = launch * K; ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
-                ctl->resid = bnorm > 0.0 ? rmax / bnorm : 0.0;
+                ctl->resid = bnorm != 0.0 ? rmax / bnorm : 0.0;
             }
             return;
         }
@@ -106,7 +106,7 @@ k_strip_jacobi(int n, const int32_t* __restrict__ cols, const double* __restrict
                     for (int s = 1; s < W; ++s) acc = fma(-lv[r][s], cur[lc[r][s - 1]], acc);
                     xn = acc * lv[r][0];          // one reciprocal per row and launch instead of K divisions
                     const int i = e0 + li;
-                    if (k == K - 1 && i >= r0 && i < r1) rmax = fmax(rmax, fabs(acc - dg[r] * xi));
+                    if (k == K - 1 && i >= r0 && i < r1) rmax = nan_max(rmax, fabs(acc - dg[r] * xi));
                 }
                 nxt[li] = xn;
             }
@@ -384,9 +384,9 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
         if (!BIG && launch > 0 && g_build == nwg) {
             const double* pr = p + ((launch - 1) & 1) * FEMFCT_MAX_PARTIALS;
             for (int k = threadIdx.x; k < nwg; k += blockDim.x) {
-                bnorm = fmax(bnorm, p[2 * FEMFCT_MAX_PARTIALS + k]);
-                rmax_prev = fmax(rmax_prev, pr[k]);
-                rsmin = fmin(rsmin, p[3 * FEMFCT_MAX_PARTIALS + k]);
+                bnorm = nan_max(bnorm, p[2 * FEMFCT_MAX_PARTIALS + k]);
+                rmax_prev = nan_max(rmax_prev, pr[k]);
+                rsmin = nan_min(rsmin, p[3 * FEMFCT_MAX_PARTIALS + k]);
             }
             block_reduce_max_max_min(bnorm, rmax_prev, rsmin, smem);
             have_rmax = true;
@@ -409,7 +409,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
         if (rmax <= rel_tol * bnorm) {
             if (wg == 0 && threadIdx.x == 0) {
                 ctl->done = 1; ctl->parity = launch & 1; ctl->iters = launch * K; ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
-                ctl->resid = bnorm > 0.0 ? rmax / bnorm : 0.0;
+                ctl->resid = bnorm != 0.0 ? rmax / bnorm : 0.0;
             }
             return;
         }
@@ -442,7 +442,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
                 double acc = bv;
 #pragma unroll
                 for (int s = 0; s < W - 1; ++s) acc = fma(-lv[s], c[g.nb[s]], acc);
-                if (k == K - 1 && g.owned) rmax = fmax(rmax, fabs(acc - dg * xn));
+                if (k == K - 1 && g.owned) rmax = nan_max(rmax, fabs(acc - dg * xn));
                 xn = acc * rdg;
             }
             xs[cur ^ 1][g.self] = xn;
@@ -464,7 +464,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
 #pragma unroll
                     for (int s = 0; s < W - 1; ++s) acc = fma(-lv[s], c[g.nb[s]], acc);
                     if (g.owned) rk[k] = fabs(acc - dg * xn);
-                    if (k == K - 1) rmax = fmax(rmax, rk[k]);
+                    if (k == K - 1) rmax = nan_max(rmax, rk[k]);
                     xn = acc * rdg;
                 }
                 xs[cur ^ 1][g.self] = xn;
@@ -482,7 +482,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
         __syncthreads();
         if (threadIdx.x < H) {
             double v = 0.0;
-            for (int w = 0; w < STRIP_T / WAVE; ++w) v = fmax(v, sk[threadIdx.x][w]);
+            for (int w = 0; w < STRIP_T / WAVE; ++w) v = nan_max(v, sk[threadIdx.x][w]);
             partk[((int64_t)bz * 16 + threadIdx.x) * FEMFCT_MAX_PARTIALS + wg] = v;
         }
     }
@@ -626,7 +626,7 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
             double acc = bv;
 #pragma unroll
             for (int s = 0; s < W - 1; ++s) acc = fma(-lv[s], c[g.nb[s]], acc);
-            if (k == K - 1 && g.owned) rmax = fmax(rmax, fabs(acc - dg * xn));
+            if (k == K - 1 && g.owned) rmax = nan_max(rmax, fabs(acc - dg * xn));
             xn = acc * rdg;
         }
         xs[cur ^ 1][g.self] = xn;
@@ -690,7 +690,7 @@ k_reduce_resid(const double* __restrict__ bigpart, int64_t count, StepCtl* __res
     if (ctl_[bz].done) return;
     const double* q = bigpart + (int64_t)bz * count;
     double v = 0.0;
-    for (int64_t k = threadIdx.x; k < count; k += blockDim.x) v = fmax(v, q[k]);
+    for (int64_t k = threadIdx.x; k < count; k += blockDim.x) v = nan_max(v, q[k]);
     v = block_reduce(v, OpMax(), 0.0, smem);
     if (threadIdx.x == 0) ctl_[bz].rs[launch & 1] = v;
 }
@@ -1382,7 +1382,7 @@ k_tile4_jacobi(int n, int N, const double* __restrict__ L_, const double* __rest
         if (rmax <= rel_tol * bnorm) {
             if (wg == 0 && threadIdx.x == 0) {
                 ctl->done = 1; ctl->parity = launch & 1; ctl->iters = launch * K; ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
-                ctl->resid = bnorm > 0.0 ? rmax / bnorm : 0.0;
+                ctl->resid = bnorm != 0.0 ? rmax / bnorm : 0.0;
             }
             return;
         }
@@ -1422,7 +1422,7 @@ k_tile4_jacobi(int n, int N, const double* __restrict__ L_, const double* __rest
                 double acc = bv[q];
 #pragma unroll
                 for (int s = 0; s < W - 1; ++s) acc = fma(-lv[q][s], cur[g[q].self + t4_off(s)], acc);
-                if (k == K - 1 && g[q].owned) rmax = fmax(rmax, fabs(acc - dg[q] * xn));
+                if (k == K - 1 && g[q].owned) rmax = nan_max(rmax, fabs(acc - dg[q] * xn));
                 xn = acc * rdg[q];
             }
             if (g[q].inside) nxt[g[q].self] = xn;
@@ -1635,7 +1635,7 @@ k_strip4_jacobi(int n, int N, const double* __restrict__ L_, const double* __res
         if (rmax <= rel_tol * bnorm) {
             if (wg == 0 && threadIdx.x == 0) {
                 ctl->done = 1; ctl->parity = launch & 1; ctl->iters = launch * K; ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
-                ctl->resid = bnorm > 0.0 ? rmax / bnorm : 0.0;
+                ctl->resid = bnorm != 0.0 ? rmax / bnorm : 0.0;
             }
             return;
         }
@@ -1706,7 +1706,7 @@ k_strip4_jacobi(int n, int N, const double* __restrict__ L_, const double* __res
             STRIP4_ROW_FMAS(acc, lv[r], x, above, below, r);
             // no validity guard: a node at distance d from the patch border is exact after k <= d sweeps whatever
             // the nodes further out hold (they stay bounded: rows are diagonally dominant, outside rows are zero)
-            if (k == K - 1 && g[r].owned) rmax = fmax(rmax, dg[r] * fabs(acc - x[r]));
+            if (k == K - 1 && g[r].owned) rmax = nan_max(rmax, dg[r] * fabs(acc - x[r]));
             xn[r] = acc;
         }
         // one workgroup = the whole mesh (check_every > 0): the residual of this sweep's input iterate is known
@@ -1715,12 +1715,12 @@ k_strip4_jacobi(int n, int N, const double* __restrict__ L_, const double* __res
             double rk = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (g[r].owned) rk = fmax(rk, dg[r] * fabs(xn[r] - x[r]));
+                if (g[r].owned) rk = nan_max(rk, dg[r] * fabs(xn[r] - x[r]));
             rk = block_reduce(rk, OpMax(), 0.0, smem);
             if (rk <= rel_tol * bnorm) {                 // x (the input of this sweep) already meets the tolerance
                 if (threadIdx.x == 0) {
                     ctl->done = 1; ctl->parity = (launch + 1) & 1; ctl->iters = launch * K + k;
-                    ctl->resid = bnorm > 0.0 ? rk / bnorm : 0.0;
+                    ctl->resid = bnorm != 0.0 ? rk / bnorm : 0.0;
                 }
                 break;
             }
@@ -1776,7 +1776,7 @@ k_strip4_jacobi_walk(int n, int N, const double* __restrict__ L_, const double* 
         if (rprev <= rel_tol * bnorm) {
             if (wg == 0 && threadIdx.x == 0) {
                 ctl->done = 1; ctl->parity = launch & 1; ctl->iters = launch * K; ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
-                ctl->resid = bnorm > 0.0 ? rprev / bnorm : 0.0;
+                ctl->resid = bnorm != 0.0 ? rprev / bnorm : 0.0;
             }
             return;
         }
@@ -1894,7 +1894,7 @@ k_strip4_jacobi_walk(int n, int N, const double* __restrict__ L_, const double* 
             for (int r = 0; r < 4; ++r) {
                 double acc = bv[r];
                 STRIP4_ROW_FMAS(acc, lv[r], x, above, below, r);
-                if (k == K - 1 && g[r].owned) rmax = fmax(rmax, dg[r] * fabs(acc - x[r]));
+                if (k == K - 1 && g[r].owned) rmax = nan_max(rmax, dg[r] * fabs(acc - x[r]));
                 xn[r] = acc;
             }
 #pragma unroll
@@ -1982,7 +1982,7 @@ k_strip_jacobi_pair_walk(int n, int N, const double* __restrict__ L_, const doub
         if (rprev <= rel_tol * bnorm) {
             if (wg == 0 && threadIdx.x == 0) {
                 ctl->done = 1; ctl->parity = launch & 1; ctl->iters = launch * K; ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
-                ctl->resid = bnorm > 0.0 ? rprev / bnorm : 0.0;
+                ctl->resid = bnorm != 0.0 ? rprev / bnorm : 0.0;
             }
             return;
         }
@@ -2254,7 +2254,7 @@ k_strip_jacobi_pair_walk(int n, int N, const double* __restrict__ L_, const doub
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const int ly = ly0 + r, gy = y0 + r;
-                        if (xowned && ly >= H && ly < H + TY && gy >= 0 && gy < N) rmax = fmax(rmax, dg[r] * fabs(x[r] - xo[r]));
+                        if (xowned && ly >= H && ly < H + TY && gy >= 0 && gy < N) rmax = nan_max(rmax, dg[r] * fabs(x[r] - xo[r]));
                     }
                 } else {
                     __syncthreads();

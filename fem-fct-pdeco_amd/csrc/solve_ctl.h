@@ -24,12 +24,12 @@ __device__ __forceinline__ DeferredPartials deferred_test_load(const double* p, 
     if (threadIdx.x < WAVE) {
 #pragma unroll 4                           // (up to 256 workgroups: all loads of the wave in flight together)
         for (int k = threadIdx.x; k < G; k += WAVE) {
-            d.r[0] = fmax(d.r[0], p[k]);
+            d.r[0] = nan_max(d.r[0], p[k]);
 #pragma unroll
             for (int s = 1; s < FEMFCT_DEFER_MAX_UNITS; ++s)
-                if (s < units) d.r[s] = fmax(d.r[s], partk[(int64_t)s * FEMFCT_MAX_PARTIALS + k]);
-            d.bn = fmax(d.bn, p[2 * FEMFCT_MAX_PARTIALS + k]);
-            d.rs = fmin(d.rs, p[3 * FEMFCT_MAX_PARTIALS + k]);
+                if (s < units) d.r[s] = nan_max(d.r[s], partk[(int64_t)s * FEMFCT_MAX_PARTIALS + k]);
+            d.bn = nan_max(d.bn, p[2 * FEMFCT_MAX_PARTIALS + k]);
+            d.rs = nan_min(d.rs, p[3 * FEMFCT_MAX_PARTIALS + k]);
         }
     }
     return d;
@@ -58,7 +58,7 @@ __device__ __forceinline__ void deferred_test_publish(StepCtl* ctl, DeferredPart
         ctl->iters = (first >= 0 ? first + 1 : units) * iters_per_unit;
         if (first >= 0 && first < units - 1) ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
         if (first < 0) ctl->flags |= FEMFCT_FLAG_SOLVER_BUDGET;
-        ctl->resid = bn > 0.0 ? rlast / bn : 0.0;
+        ctl->resid = bn != 0.0 ? rlast / bn : 0.0;
     }
 }
 
@@ -79,7 +79,7 @@ __device__ __forceinline__ void finalize_solve(StepCtl* ctl, double* p, int G, i
         if (leader && threadIdx.x == 0) {
             const double bn = ctl->bnorm;
             ctl->iters = (first >= 0) ? (budget - 1) * iters_per_unit + first + 1 : budget * iters_per_unit;
-            ctl->resid = bn > 0.0 ? rlast / bn : 0.0;
+            ctl->resid = bn != 0.0 ? rlast / bn : 0.0;
             if (first < 0) ctl->flags |= FEMFCT_FLAG_SOLVER_BUDGET;
         }
         return;
@@ -92,7 +92,7 @@ __device__ __forceinline__ void finalize_solve(StepCtl* ctl, double* p, int G, i
     if (leader && threadIdx.x == 0) {
         double bn = ctl->bnorm;
         ctl->iters = budget * iters_per_unit;
-        ctl->resid = bn > 0.0 ? rmax / bn : 0.0;
+        ctl->resid = bn != 0.0 ? rmax / bn : 0.0;
         if (!(rmax <= rel_tol * bn)) ctl->flags |= FEMFCT_FLAG_SOLVER_BUDGET;
     }
 }

@@ -158,7 +158,7 @@ int femfct_run_sweep(femfct_ctx* ctx, int kind, int32_t num_steps, int32_t batch
                 kworst = std::max(kworst, kl[k].iters);
                 if ((kl[k].flags & FEMFCT_FLAG_SOLVER_BUDGET) || !(kl[k].resid == kl[k].resid)) {
                     kshort = true;
-                    kworst_res = std::max(kworst_res, kl[k].resid == kl[k].resid ? kl[k].resid : 1.0);
+                    kworst_res = std::max(kworst_res, kl[k].resid == kl[k].resid ? kl[k].resid : INFINITY);   // NaN: diverged
                 }
             }
         }
@@ -217,7 +217,8 @@ int femfct_run_sweep(femfct_ctx* ctx, int kind, int32_t num_steps, int32_t batch
                 femfct_drop_graphs(ctx);
                 continue;
             }
-            if (budget >= ctx->max_iters)
+            // a residual that is not finite (NaN or Inf in the data) stays so whatever the budget: fail now
+            if (budget >= ctx->max_iters || !(worst_res < INFINITY))
                 return femfct_fail(ctx, FEMFCT_ERR_NOT_CONVERGED,
                                    "low-order solve: residual %.3e after %d %s (tol %.1e)", worst_res, budget,
                                    ctx->solver == FEMFCT_SOLVER_BICGSTAB ? "BiCGStab iterations" : "Jacobi sweeps",
@@ -231,7 +232,7 @@ int femfct_run_sweep(femfct_ctx* ctx, int kind, int32_t num_steps, int32_t batch
             if (!(kworst_res < 10.0) || kbudget >= ctx->kry_max_iters) ctx->kind_cheb_off.insert(kind);
             else ctx->kind_kbudget[kkey] = std::min(ctx->kry_max_iters, std::max(kbudget + 10, kworst + kworst / 10 + 5));
         } else if (kshort) {
-            if (kbudget >= ctx->kry_max_iters)
+            if (kbudget >= ctx->kry_max_iters || !(kworst_res < INFINITY))
                 return femfct_fail(ctx, FEMFCT_ERR_NOT_CONVERGED,
                                    "BiCGStab: residual %.3e after %d iterations (tol %.1e)", kworst_res, kbudget,
                                    ctx->kry_tol);

@@ -168,7 +168,7 @@ int femfct_bicgstab(femfct_ctx* ctx, const double* mat_ell, int32_t mat_shared, 
         for (int b = 0; b < batch; ++b) {
             worst = std::max(worst, h[b].iters);
             bool nan = !(h[b].resid == h[b].resid);
-            if ((h[b].flags & FEMFCT_FLAG_SOLVER_BUDGET) || nan) { bad = true; wres = std::max(wres, nan ? 1.0 : h[b].resid); }
+            if ((h[b].flags & FEMFCT_FLAG_SOLVER_BUDGET) || nan) { bad = true; wres = nan ? h[b].resid : std::max(wres, h[b].resid); }
             if (info_host) {
                 info_host[b].flags = h[b].flags;
                 info_host[b].solver_iters = h[b].iters;
@@ -180,7 +180,8 @@ int femfct_bicgstab(femfct_ctx* ctx, const double* mat_ell, int32_t mat_shared, 
             ctx->kry_budget = std::min(ctx->kry_max_iters, std::max(8, worst + worst / 4 + 2));
             return FEMFCT_OK;
         }
-        if (budget >= ctx->kry_max_iters)
+        // (a residual that is not finite stays so whatever the budget)
+        if (budget >= ctx->kry_max_iters || !(wres < INFINITY))
             return femfct_fail(ctx, FEMFCT_ERR_NOT_CONVERGED, "BiCGStab: residual %.3e after %d iterations (tol %.1e)",
                                wres, budget, ctx->kry_tol);
         ctx->kry_budget = std::min(ctx->kry_max_iters, budget * 2);
