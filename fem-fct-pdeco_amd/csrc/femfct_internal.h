@@ -250,7 +250,13 @@ static inline uint64_t key_bits(int32_t v) { return (uint64_t)(int64_t)v; }
 template <class F>
 int femfct_run_graph(femfct_ctx* ctx, const femfct_ctx::GraphKey& key, F&& enqueue);
 
-// strip-fused kernels (kernels_strip.hip)
+// multi-sweep kernels, one file per family; the regime of a step: femfct_kernel_regime (ctx.hip)
+// the 2-D families apply: not switched off (femfct_set_fusion), 7-point stencil with implicit columns (structured mesh)
+static inline bool femfct_tiles_usable(const femfct_ctx* ctx) {
+    return ctx->use_strips && ctx->use_tiles && ctx->implicit_cols && ctx->W == 7;
+}
+
+// -- kernels_rowstrip.hip: row strips, any ELL pattern
 struct StripPlan { int K, R, bw, rpt, S; };
 bool femfct_strip_plan(const femfct_ctx* ctx, StripPlan* pl);
 int femfct_strip_init(femfct_ctx* ctx);
@@ -260,40 +266,44 @@ int femfct_enqueue_strip_cheb(femfct_ctx* ctx, const StripPlan& pl, const double
                               const double* in_old, double* y_out, int k_first, int k_last, const double* omegas,
                               double md_scale, double* bufA0, double* bufA1, double* bufB0, double* bufB1,
                               int32_t batch);
+
+// -- kernels_tile32.hip: 32 x 32 tiles of the structured mesh, latency regime
 struct TilePlan { int tiles, K, H; };
 bool femfct_tile_plan(const femfct_ctx* ctx, TilePlan* pl, bool need_partials = true, int budget = 0, int batch = 1);
-int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double* L, const double* b, double* xa,
-                               double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch = 0, int defer = 0);
+bool femfct_tile_big(const femfct_ctx* ctx, const TilePlan& pl);   // more workgroups than in-kernel partials
+bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch);
+bool femfct_geom_mass(const femfct_ctx* ctx);   // M may be derived from the cell geometry instead of loaded
 int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, struct MatRef A, const double* Nm, int32_t nshared,
                                      struct VecRef rhs, int64_t rhs_bstride, struct VecRef u_n, int64_t u_bstride, double dt,
                                      int32_t batch, bool pre = false);
 int femfct_enqueue_low_seq(femfct_ctx* ctx, const double* A, double* L, double* D, int32_t entries, double dt);
-bool femfct_tile_big(const femfct_ctx* ctx, const TilePlan& pl);   // more workgroups than in-kernel partials
+int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double* L, const double* b, double* xa,
+                               double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch = 0, int defer = 0);
+// k_reduce_resid behind a launch that left `count` residual partials per batch member in d_bigpart (both 2-D families;
+// internal to the library: not exported)
+__attribute__((visibility("hidden"))) void femfct_launch_reduce_resid(femfct_ctx* ctx, int64_t count, int launch, int32_t batch);
+int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, struct MatRef A, struct VecRef rhs, int64_t rhs_bstride, double* ulow,
+                                  int budget_units, int part_count, int iters_per_unit, int exact_k, int iters,
+                                  const double* omegas, double md_scale, int32_t batch, int* tail_first = nullptr);
 int femfct_enqueue_tile_cheb(femfct_ctx* ctx, const TilePlan& pl, const double* b, const double* in_mid,
                              const double* in_old, double* y_out, int k_first, int k_last, const double* omegas,
                              double md_scale, double* bufA0, double* bufA1, double* bufB0, double* bufB1, int32_t batch,
                              const struct ChebIO* io = nullptr);
-int femfct_enqueue_tile_flux_limit(femfct_ctx* ctx, const double* D, const double* ulow, const double* du, double dt,
-                                   struct VecRef out, int64_t out_bstride, int32_t batch, bool* fuse_end_io, int half_d = 0);
-int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, struct MatRef A, struct VecRef rhs, int64_t rhs_bstride, double* ulow,
-                                  int budget_units, int part_count, int iters_per_unit, int exact_k, int iters,
-                                  const double* omegas, double md_scale, int32_t batch, int* tail_first = nullptr);
-bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch);
-bool femfct_rotation_is_geometric(femfct_ctx* ctx, const double* Arot, double* om_out);   // kernels_asm.hip
-bool femfct_geom_mass(const femfct_ctx* ctx);   // M may be derived from the cell geometry instead of loaded
 int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const double* in_mid, const double* in_old,
                                         int k_first, int k_last, const double* omegas, double md_scale, struct MatRef D,
                                         const double* ulow, double dt, struct VecRef out, int64_t out_bstride, int32_t batch,
                                         bool fuse_end);
-int femfct_tile4_init(femfct_ctx* ctx);
+int femfct_enqueue_tile_flux_limit(femfct_ctx* ctx, const double* D, const double* ulow, const double* du, double dt,
+                                   struct VecRef out, int64_t out_bstride, int32_t batch, bool* fuse_end_io, int half_d = 0);
+
+// -- kernels_patch64.hip: 64-wide patches, register strips and walkers, bandwidth regime
 bool femfct_tile4_wanted(const femfct_ctx* ctx, int32_t batch);
+bool femfct_single_patch(const femfct_ctx* ctx, int32_t batch);
 int femfct_tile4_tiles(const femfct_ctx* ctx, int H = 8);
+int femfct_tile4_halo(const femfct_ctx* ctx, int sweeps);
 int femfct_tile4_walkers(const femfct_ctx* ctx, int H, int32_t batch, bool pair);   // 0: one workgroup per patch
 bool femfct_jacobi_pair_wanted(const femfct_ctx* ctx, int H, int32_t batch, bool have_lmask, bool assume_upwind_rows = false);
-int femfct_tile4_halo(const femfct_ctx* ctx, int sweeps);
-bool femfct_single_patch(const femfct_ctx* ctx, int32_t batch);
-// launches and sweeps per launch the low-order solve of femfct_enqueue_step_mat will use for a budget
-bool femfct_jacobi_plan(const femfct_ctx* ctx, int budget, int batch, int* K, int* launches);
+int femfct_tile4_init(femfct_ctx* ctx);
 int femfct_enqueue_tile4_jacobi(femfct_ctx* ctx, const double* L, const double* b, double* xa, double* xb, int launch,
                                 int g_build, int32_t batch, int H = 8, int K = 8, int check_every = 0,
                                 const uint8_t* lmask = nullptr);
@@ -301,6 +311,10 @@ int femfct_enqueue_tile4_cheb(femfct_ctx* ctx, const double* b, const double* in
                               int k_first, int k_last, const double* omegas, double md_scale, double* bufA0, double* bufA1,
                               double* bufB0, double* bufB1, int32_t batch,
                               const struct ChebIO* io = nullptr);
+
+bool femfct_rotation_is_geometric(femfct_ctx* ctx, const double* Arot, double* om_out);   // kernels_asm.hip
+// launches and sweeps per launch the low-order solve of femfct_enqueue_step_mat will use for a budget
+bool femfct_jacobi_plan(const femfct_ctx* ctx, int budget, int batch, int* K, int* launches);
 // one workgroup per trajectory (kernels_mesh.hip)
 bool femfct_mesh_step_wanted(const femfct_ctx* ctx, int32_t batch, bool have_nm = false);
 int femfct_enqueue_mesh_step(femfct_ctx* ctx, struct MatRef A, const double* Nm, int32_t nshared, struct VecRef rhs,

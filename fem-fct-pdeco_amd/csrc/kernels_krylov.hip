@@ -449,7 +449,7 @@ static double element_lambda_min(double h, double tau) {
 bool femfct_species_cheb(const femfct_ctx* ctx, int kind) {
     if (ctx->species_solver != 0 || ctx->kind_cheb_off.count(kind)) return false;
     if (ctx->structured && femfct_mesh_solve_fits(ctx)) return true;     // one workgroup per system (any ordering)
-    if (!ctx->use_strips || !ctx->use_tiles || !ctx->implicit_cols || ctx->W != 7) return false;
+    if (!femfct_tiles_usable(ctx)) return false;
     TilePlan tp;
     return femfct_tile_plan(ctx, &tp, false);
 }

@@ -1,0 +1,995 @@
+// 32 x 32 tile kernels of the structured mesh in vertex order -- the LATENCY regime (the config meshes, n = 1681 / 6561:
+// a sweep moves < 1 MB and costs one dependent kernel boundary, so the step is bound by its number of launches).
+// Selected by femfct_tile_plan (policy block at the end of this file, with femfct_tile_big and
+// femfct_cheb_flux_fusable); larger meshes and batches go to kernels_patch64.hip, other patterns to kernels_rowstrip.hip.
+// A step of this regime, launch by launch: k_tile_build_jacobi (operator + first sweeps; k_low_seq builds the operators
+// of a whole sequence beforehand), k_tile_jacobi, k_tile_dudt_cheb, k_tile_cheb, then k_tile_cheb_flux_limit or
+// k_tile_flux_limit.
+//
+// A 1024-thread workgroup stages a 32 x 32 patch = (32 - 2H)^2 tile + halo H on every side -- one node per thread, the
+// node's matrix row in registers, the iterate in LDS -- and runs up to H sweeps per launch (the halo shrinks by one
+// ring per sweep).  H = 8 on large grids (least re-reading), 8..13 in the latency regime (fewest launches: see
+// femfct_tile_plan).  Compared with row strips there is no column table to load and the work spreads over
+// (N / (32 - 2H))^2 workgroups.
+#include "femfct_internal.h"
+#include "device_utils.h"
+#include "solve_ctl.h"
+#include "forms.h"
+#include "step_end.h"
+#include "sweep_common.h"
+
+#include <math.h>
+
+#define TILE_T 16
+#define TILE_H 8
+#define TILE_L 32
+#define TILE_LD 33   // padded LDS row
+#define TILE_HMAX 13 // deepest halo instantiated (Jacobi, latency regime)
+
+namespace {
+
+struct TileGeom {
+    int lx, ly, gx, gy, i;
+    bool inside, owned;
+    int kvalid;          // the node's value is exact for sweeps k < kvalid
+    int nb[6];           // LDS offsets of the six neighbours (clamped into the patch)
+    int self;
+};
+
+template <int T = TILE_T, int H = TILE_H, int PL = TILE_L>
+__device__ __forceinline__ TileGeom tile_geom(int N) {
+    static_assert(T + 2 * H == PL, "patch edge = tile + 2 halos");
+    constexpr int PLD = PL + 1;
+    TileGeom g;
+    g.lx = threadIdx.x % PL;
+    g.ly = threadIdx.x / PL;
+    const int x0 = blockIdx.x * T - H, y0 = blockIdx.y * T - H;
+    g.gx = x0 + g.lx;
+    g.gy = y0 + g.ly;
+    g.inside = g.gx >= 0 && g.gx < N && g.gy >= 0 && g.gy < N;
+    g.i = g.inside ? g.gy * N + g.gx : 0;
+    g.owned = g.inside && g.lx >= H && g.lx < H + T && g.ly >= H && g.ly < H + T;
+    int kv = 1 << 20;
+    if (x0 > 0) kv = min(kv, g.lx);
+    if (x0 + PL - 1 < N - 1) kv = min(kv, PL - 1 - g.lx);
+    if (y0 > 0) kv = min(kv, g.ly);
+    if (y0 + PL - 1 < N - 1) kv = min(kv, PL - 1 - g.ly);
+    g.kvalid = g.inside ? kv : 0;
+    const int dx[6] = {1, 1, 0, -1, -1, 0}, dy[6] = {0, 1, 1, 0, -1, -1};
+    g.self = g.ly * PLD + g.lx;
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        int nx = min(max(g.lx + dx[s], 0), PL - 1), ny = min(max(g.ly + dy[s], 0), PL - 1);
+        g.nb[s] = ny * PLD + nx;
+    }
+    return g;
+}
+
+// BIG = 1: grids with more workgroups than in-kernel partials (bandwidth regime); the residual maxima
+// go through k_reduce_resid.  A template parameter so that profiles list the two regimes separately.
+template <int H, int EXACT, int BIG>
+__global__ void __launch_bounds__(STRIP_T)
+k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restrict__ b_, double* __restrict__ xa_,
+              double* __restrict__ xb_, double* __restrict__ part, StepCtl* __restrict__ ctl_, int launch, int K,
+              int g_build, double rel_tol, double* __restrict__ bigpart, double* __restrict__ partk, int bn_launch,
+              int defer) {
+    constexpr int W = 7;
+    __shared__ double xs[2][TILE_L * TILE_LD];
+    __shared__ double smem[96];
+    const int bz = blockIdx.z;
+    StepCtl* ctl = ctl_ + bz;
+    if (!defer && ctl->done) return;       // (defer: nothing sets `done` before this launch -- one dependent round trip less)
+    double* p = part + (int64_t)bz * 4 * FEMFCT_MAX_PARTIALS;
+    const int nwg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x;
+    double bnorm;
+    // ||b||, min row sum: reduced from the partials of the kernel that built L (k_build_low before launch 0,
+    // or the fused k_tile_build_jacobi = launch 0 itself, then bn_launch = 1); launch >= 1 also tests the
+    // residual the previous launch left.  In the fused case all three come out of one reduction pass.
+    double rmax_prev = 0.0;
+    bool have_rmax = false;
+    // defer: a later launch of a solve of <= 4 launches whose first launch built the operator -- nothing is reduced and nothing
+    // tested here (the test of launch 0's residual practically never passes; waiting for its partials costs this launch
+    // ~2 us of its ~10); workgroup 0 of k_tile_dudt_cheb reduces everything at once (solve_ctl.h, deferred_test_*)
+    if (defer) {
+        bnorm = 0.0;
+    } else if (launch == bn_launch) {
+        double rsmin = INFINITY;
+        bnorm = 0.0;
+        if (!BIG && launch > 0 && g_build == nwg) {
+            const double* pr = p + ((launch - 1) & 1) * FEMFCT_MAX_PARTIALS;
+            for (int k = threadIdx.x; k < nwg; k += blockDim.x) {
+                bnorm = nan_max(bnorm, p[2 * FEMFCT_MAX_PARTIALS + k]);
+                rmax_prev = nan_max(rmax_prev, pr[k]);
+                rsmin = nan_min(rsmin, p[3 * FEMFCT_MAX_PARTIALS + k]);
+            }
+            block_reduce_max_max_min(bnorm, rmax_prev, rsmin, smem);
+            have_rmax = true;
+        } else {
+            bnorm = reduce_partials(p + 2 * FEMFCT_MAX_PARTIALS, g_build, OpMax(), 0.0, smem);
+            rsmin = reduce_partials(p + 3 * FEMFCT_MAX_PARTIALS, g_build, OpMin(), INFINITY, smem);
+        }
+        if (wg == 0 && threadIdx.x == 0) {
+            ctl->bnorm = bnorm;
+            ctl->min_rowsum = rsmin;
+            if (!(rsmin > 0.0)) ctl->flags |= FEMFCT_FLAG_MMATRIX_ROWSUM;
+        }
+    } else {
+        bnorm = ctl->bnorm;
+    }
+    if (launch > 0 && !defer) {
+        double rmax = have_rmax ? rmax_prev
+                      : BIG   ? ctl->rs[(launch - 1) & 1]
+                              : reduce_partials(p + ((launch - 1) & 1) * FEMFCT_MAX_PARTIALS, nwg, OpMax(), 0.0, smem);
+        if (rmax <= rel_tol * bnorm) {
+            if (wg == 0 && threadIdx.x == 0) {
+                ctl->done = 1; ctl->parity = launch & 1; ctl->iters = launch * K; ctl->flags |= FEMFCT_FLAG_COARSE_ITERS;
+                ctl->resid = bnorm != 0.0 ? rmax / bnorm : 0.0;
+            }
+            return;
+        }
+    }
+    const int64_t moff = (int64_t)bz * W * n, voff = (int64_t)bz * n;
+    const double* L = L_ + moff;
+    const double* xin = ((launch & 1) ? xb_ : xa_) + voff;
+    double* xout = ((launch & 1) ? xa_ : xb_) + voff;
+    const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
+    double lv[W - 1], dg = 1.0, rdg = 1.0, bv = 0.0, xi = 0.0;
+#pragma unroll
+    for (int s = 0; s < W - 1; ++s) lv[s] = 0.0;
+    if (g.inside) {
+        dg = L[g.i];
+        rdg = 1.0 / dg;
+#pragma unroll
+        for (int s = 1; s < W; ++s) lv[s - 1] = L[(int64_t)s * n + g.i];
+        bv = b_[voff + g.i];
+        xi = xin[g.i];
+    }
+    xs[0][g.self] = xi;
+    __syncthreads();
+    double rmax = 0.0;
+    int cur = 0;
+    if (!EXACT) {
+        for (int k = 0; k < K; ++k) {
+            const double* c = xs[cur];
+            double xn = c[g.self];
+            if (k < g.kvalid) {
+                double acc = bv;
+#pragma unroll
+                for (int s = 0; s < W - 1; ++s) acc = fma(-lv[s], c[g.nb[s]], acc);
+                if (k == K - 1 && g.owned) rmax = nan_max(rmax, fabs(acc - dg * xn));
+                xn = acc * rdg;
+            }
+            xs[cur ^ 1][g.self] = xn;
+            __syncthreads();
+            cur ^= 1;
+        }
+    } else {
+        // last launch of the budget, optional: log the residual of every sweep's input so that the
+        // host learns the exact sweep count (fully unrolled: per-sweep values stay in registers)
+        double rk[H];
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+            rk[k] = 0.0;
+            if (k < K) {
+                const double* c = xs[cur];
+                double xn = c[g.self];
+                if (k < g.kvalid) {
+                    double acc = bv;
+#pragma unroll
+                    for (int s = 0; s < W - 1; ++s) acc = fma(-lv[s], c[g.nb[s]], acc);
+                    if (g.owned) rk[k] = fabs(acc - dg * xn);
+                    if (k == K - 1) rmax = nan_max(rmax, rk[k]);
+                    xn = acc * rdg;
+                }
+                xs[cur ^ 1][g.self] = xn;
+                __syncthreads();
+                cur ^= 1;
+            }
+        }
+        __shared__ double sk[H][STRIP_T / WAVE];
+        const int wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+            double v = wave_reduce(rk[k], OpMax());
+            if (lane == 0) sk[k][wid] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < H) {
+            double v = 0.0;
+            for (int w = 0; w < STRIP_T / WAVE; ++w) v = nan_max(v, sk[threadIdx.x][w]);
+            partk[((int64_t)bz * 16 + threadIdx.x) * FEMFCT_MAX_PARTIALS + wg] = v;
+        }
+    }
+    if (g.owned) xout[g.i] = xs[cur][g.self];
+    rmax = block_reduce(rmax, OpMax(), 0.0, smem);
+    if (threadIdx.x == 0) {
+        if (BIG) bigpart[(int64_t)bz * nwg + wg] = rmax;
+        else if (defer) partk[((int64_t)bz * 16 + launch) * FEMFCT_MAX_PARTIALS + wg] = rmax;   // one slot per launch
+        else p[(launch & 1) * FEMFCT_MAX_PARTIALS + wg] = rmax;
+    }
+}
+
+// Launch 0 of the low-order solve with the construction of the low-order operator folded in
+// (what k_build_low does, helpers.py:1769-1780, same expressions in the same order => bitwise the same
+// L, D, b): every thread builds the row of its patch node from A (a_ji comes from the neighbour thread
+// through LDS, three slots at a time), the tile's owned rows are stored for the later launches / the
+// limiter, then K Jacobi sweeps run as in k_tile_jacobi.  Saves one dependent launch per time step.
+// PRE = 1: the operator was built before the sweep (k_low_seq): A_ref is the L_k sequence, read instead of built (no
+// a_ji exchange, no D store: the limiter reads D_k from the sequence); the owned rows of L still go to L_ for launch 1.
+template <int H, int PRE>
+__global__ void __launch_bounds__(STRIP_T)
+k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, int nshared,
+                    VecRef rhs_ref, int64_t rhs_bstride, VecRef u_ref, int64_t u_bstride,
+                    const double* __restrict__ ml, double dt, double* __restrict__ L_, double* __restrict__ D_,
+                    double* __restrict__ b_, double* __restrict__ xb_, double* __restrict__ part,
+                    StepCtl* __restrict__ ctl_, int K) {
+    constexpr int W = 7;
+    __shared__ double xs[2][TILE_L * TILE_LD];
+    __shared__ double as[PRE ? 1 : 3][TILE_L * TILE_LD];
+    __shared__ double smem[96];
+    const int bz = blockIdx.z;
+    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
+    double* p = part + (int64_t)bz * 4 * FEMFCT_MAX_PARTIALS;
+    if (wg == 0 && threadIdx.x == 0) {
+        StepCtl* c = ctl_ + bz;
+        c->flags = 0; c->iters = 0; c->done = 0; c->parity = 0; c->resid = 0.0; c->bnorm = 0.0;
+        c->min_rowsum = 0.0;
+    }
+    const int64_t moff = (int64_t)bz * W * n, voff = (int64_t)bz * n;
+    const double* A = mat_ptr(A_ref, bz);
+    const double* Nm = N_ ? N_ + (nshared ? 0 : moff) : nullptr;
+    const double* rhs = vec_ptr(rhs_ref);
+    if (rhs) rhs += bz * rhs_bstride;
+    const double* u = vec_ptr(u_ref) + bz * u_bstride;
+    const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
+    double lv[W - 1], dv[W - 1], dsum = 0.0, rs = 0.0;
+    double dg = 1.0, rdg = 1.0, bv = 0.0, xi = 0.0;
+    if constexpr (PRE) {
+        // the rows k_low_seq built (bitwise those of the branch below); the row sum in the same order
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) lv[s] = 0.0;
+        if (g.inside) {
+            dg = A[g.i];
+#pragma unroll
+            for (int s = 1; s < W; ++s) lv[s - 1] = A[(int64_t)s * n + g.i];
+        }
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) rs += lv[s];
+        if (g.inside) {
+            const double mli = ml[g.i];
+            rs += dg;
+            rdg = 1.0 / dg;
+            xi = u[g.i];
+            bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+        }
+    } else {
+        // neighbour s exists in the grid (otherwise the ELL slot is padding: column = row, value 0)
+        const int dx[6] = {1, 1, 0, -1, -1, 0}, dy[6] = {0, 1, 1, 0, -1, -1};
+        bool ex[W - 1];
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const int nx = g.gx + dx[s], ny = g.gy + dy[s];
+            ex[s] = g.inside && nx >= 0 && nx < N && ny >= 0 && ny < N;
+        }
+        double av[W - 1], at[W - 1], a0 = 0.0;
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) av[s] = 0.0;
+        if (g.inside) {
+            a0 = A[g.i];
+#pragma unroll
+            for (int s = 1; s < W; ++s) av[s - 1] = A[(int64_t)s * n + g.i];
+        }
+        // a_ji of slot s lives in row j at the opposite slot: slots E,NE,N <-> W,SW,S
+#pragma unroll
+        for (int s = 0; s < 3; ++s) as[s][g.self] = av[s + 3];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 3; ++s) at[s] = as[s][g.nb[s]];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 3; ++s) as[s][g.self] = av[s];
+        __syncthreads();
+#pragma unroll
+        for (int s = 3; s < 6; ++s) at[s] = as[s - 3][g.nb[s]];
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const double a = av[s];
+            const double d = ex[s] ? fmax(0.0, fmax(a, at[s])) : 0.0;   // d_ij = max(0, a_ij, a_ji)
+            dsum += d;
+            double l = dt * (a - d);
+            if (Nm && g.inside) l += dt * Nm[(int64_t)(s + 1) * n + g.i];
+            lv[s] = l;
+            dv[s] = d;
+            rs += l;
+        }
+        if (g.inside) {
+            const double mli = ml[g.i];
+            double ld = mli + dt * (a0 + dsum);                         // d_ii = -sum_j d_ij
+            if (Nm) ld += dt * Nm[g.i];
+            rs += ld;
+            dg = ld;
+            rdg = 1.0 / dg;
+            xi = u[g.i];
+            bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+        }
+    }
+    double bmax = 0.0, rsmin = INFINITY;
+    if (g.owned) {
+        double* L = L_ + moff;
+        L[g.i] = dg;
+#pragma unroll
+        for (int s = 1; s < W; ++s) L[(int64_t)s * n + g.i] = lv[s - 1];
+        if constexpr (!PRE) {
+            double* D = D_ + moff;
+            D[g.i] = -dsum;
+#pragma unroll
+            for (int s = 1; s < W; ++s) D[(int64_t)s * n + g.i] = dv[s - 1];
+        }
+        b_[voff + g.i] = bv;
+        bmax = fabs(bv);
+        rsmin = rs;
+    }
+    xs[0][g.self] = xi;
+    __syncthreads();
+    double rmax = 0.0;
+    int cur = 0;
+    for (int k = 0; k < K; ++k) {
+        const double* c = xs[cur];
+        double xn = c[g.self];
+        if (k < g.kvalid) {
+            double acc = bv;
+#pragma unroll
+            for (int s = 0; s < W - 1; ++s) acc = fma(-lv[s], c[g.nb[s]], acc);
+            if (k == K - 1 && g.owned) rmax = nan_max(rmax, fabs(acc - dg * xn));
+            xn = acc * rdg;
+        }
+        xs[cur ^ 1][g.self] = xn;
+        __syncthreads();
+        cur ^= 1;
+    }
+    if (g.owned) xb_[voff + g.i] = xs[cur][g.self];
+    block_reduce_max_max_min(rmax, bmax, rsmin, smem);
+    if (threadIdx.x == 0) {
+        p[wg] = rmax;
+        p[2 * FEMFCT_MAX_PARTIALS + wg] = bmax;
+        p[3 * FEMFCT_MAX_PARTIALS + wg] = rsmin;
+    }
+}
+
+// The low-order operator of every entry of a pre-assembled sequence, once before the sweep (FEMFCT_PREBUILD_LOW):
+// L_k = M_L + dt (A_k - D_k) and D_k depend on the control only.  The expressions and their order are those of
+// k_tile_build_jacobi (no non-flux matrix), so the bits are the same; a_ji is read from the neighbour's row.
+// Structured mesh in vertex order; blockIdx.y = sequence entry (as k_ops_solidbody writes them).
+__global__ void __launch_bounds__(256)
+k_low_seq(int n, int N, const double* __restrict__ A_, const double* __restrict__ ml, double dt, double* __restrict__ L_,
+          double* __restrict__ D_) {
+    constexpr int W = 7;
+    const int64_t off = (int64_t)blockIdx.y * W * n;
+    const double* A = A_ + off;
+    double* L = L_ + off;
+    double* D = D_ + off;
+    const int dx[6] = {1, 1, 0, -1, -1, 0}, dy[6] = {0, 1, 1, 0, -1, -1};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int gx = i % N, gy = i / N;
+        double av[W - 1], at[W - 1];
+        bool ex[W - 1];
+        const double a0 = A[i];
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const int nx = gx + dx[s], ny = gy + dy[s];
+            ex[s] = nx >= 0 && nx < N && ny >= 0 && ny < N;
+            av[s] = A[(int64_t)(s + 1) * n + i];
+            // a_ji of slot s lives in row j at the opposite slot: slots E,NE,N <-> W,SW,S
+            at[s] = ex[s] ? A[(int64_t)(s < 3 ? s + 4 : s - 2) * n + ny * N + nx] : 0.0;
+        }
+        double dsum = 0.0;
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const double a = av[s];
+            const double d = ex[s] ? fmax(0.0, fmax(a, at[s])) : 0.0;   // d_ij = max(0, a_ij, a_ji)
+            dsum += d;
+            L[(int64_t)(s + 1) * n + i] = dt * (a - d);
+            D[(int64_t)(s + 1) * n + i] = d;
+        }
+        L[i] = ml[i] + dt * (a0 + dsum);                                // d_ii = -sum_j d_ij
+        D[i] = -dsum;
+    }
+}
+
+// one block per batch member: max over the residual partials of a fused launch on a large grid
+__global__ void __launch_bounds__(STRIP_T)
+k_reduce_resid(const double* __restrict__ bigpart, int64_t count, StepCtl* __restrict__ ctl_, int launch) {
+    __shared__ double smem[32];
+    const int bz = blockIdx.x;
+    if (ctl_[bz].done) return;
+    const double* q = bigpart + (int64_t)bz * count;
+    double v = 0.0;
+    for (int64_t k = threadIdx.x; k < count; k += blockDim.x) v = nan_max(v, q[k]);
+    v = block_reduce(v, OpMax(), 0.0, smem);
+    if (threadIdx.x == 0) ctl_[bz].rs[launch & 1] = v;
+}
+
+template <int H>
+__global__ void __launch_bounds__(STRIP_T)
+k_tile_cheb(int n, int N, const double* __restrict__ M, const double* __restrict__ b_, const double* __restrict__ ymid_,
+            const double* __restrict__ yold_, double* __restrict__ omid_, double* __restrict__ oold_, int K,
+            CheOmegas om, double md_scale, ChebIO cio) {
+    constexpr int W = 7;
+    __shared__ double ys[3][TILE_L * TILE_LD];
+    const int64_t voff = (int64_t)blockIdx.z * n;
+    if (cio.mat) M = cio.mat + (int64_t)blockIdx.z * cio.mat_bs;
+    if (cio.scale_dev) md_scale = cio.scale_dev[blockIdx.z];
+    const double* omd = cio.om_dev ? cio.om_dev + (int64_t)blockIdx.z * cio.om_bs + cio.k0 : nullptr;
+    if (cio.mid_ref.base) ymid_ = vec_ptr(cio.mid_ref) + (int64_t)blockIdx.z * cio.mid_bs - voff;
+    if (cio.out_ref.base) omid_ = const_cast<double*>(vec_ptr(cio.out_ref)) + (int64_t)blockIdx.z * cio.out_bs - voff;
+    const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
+    double mv[W - 1], md = 1.0, rmd = 1.0, bv = 0.0, ym = 0.0, yo = 0.0;
+#pragma unroll
+    for (int s = 0; s < W - 1; ++s) mv[s] = 0.0;
+    if (g.inside) {
+        md = M[g.i];
+        rmd = 1.0 / (md_scale * md);
+#pragma unroll
+        for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+        bv = b_[voff + g.i];
+        if (ymid_) ym = ymid_[voff + g.i];
+        if (yold_) yo = yold_[voff + g.i];
+    }
+    ys[0][g.self] = yo;
+    ys[1][g.self] = ym;
+    __syncthreads();
+    int io = 0, im = 1, in_ = 2;
+    for (int k = 0; k < K; ++k) {
+        const double* ymd = ys[im];
+        const double ymv = ymd[g.self];
+        double yn = ymv;
+        if (k < g.kvalid) {
+            double acc = md * ymv;
+#pragma unroll
+            for (int s = 0; s < W - 1; ++s) acc = fma(mv[s], ymd[g.nb[s]], acc);
+            const double z = (bv - acc) * rmd;
+            const double yov = ys[io][g.self];
+            const double wk = omd ? omd[k] : om.w[k];
+            yn = wk * (z + ymv - yov) + yov;
+        }
+        ys[in_][g.self] = yn;
+        __syncthreads();
+        int t = io; io = im; im = in_; in_ = t;
+    }
+    if (g.owned) {
+        omid_[voff + g.i] = ys[im][g.self];
+        if (oold_) oold_[voff + g.i] = ys[io][g.self];
+    }
+}
+
+
+// flux + Zalesak limiter + explicit correction in one launch (helpers.py:1818-1870): a 12 x 12
+// tile with a halo of two rings (16 x 16 patch, 256 threads) (R+- of the first ring needs u_L, du/dt of the second);
+// F_ij stays in registers, R+- goes through LDS.
+#define FL_H 2
+// (two 1024-thread workgroups per CU need <= 64 VGPRs: the second launch-bound argument is waves per SIMD)
+// LDS slot of neighbour s of this thread's node (clamped into the patch, as TileGeom::nb), recomputed from the thread
+// index at every use: kept in registers across the limiter's three phases the six slots are what the 32-patch variant
+// (64-VGPR limit) spills -- 12 bytes per lane, 66 MB of scratch traffic per launch at 2049^2
+template <int PL>
+__device__ __forceinline__ int fl_nb(int s) {
+    const int lx = threadIdx.x % PL, ly = threadIdx.x / PL;
+    const int dx = (s == 0 || s == 1) ? 1 : (s == 3 || s == 4) ? -1 : 0;
+    const int dy = (s == 1 || s == 2) ? 1 : (s == 4 || s == 5) ? -1 : 0;
+    return min(max(ly + dy, 0), PL - 1) * (PL + 1) + min(max(lx + dx, 0), PL - 1);
+}
+
+template <int FL_L, int GEOM, int HALFD>   // patch edge: 16 (256 threads, many workgroups: small meshes) or 32 (less halo re-reading)
+__global__ void __launch_bounds__(FL_L * FL_L, FL_L == 32 ? 8 : 1)
+k_tile_flux_limit(int n, int N, double h, const double* __restrict__ M, const double* __restrict__ D_,
+                  const double* __restrict__ ulow_, const double* __restrict__ du_, const double* __restrict__ ml,
+                  double dt, VecRef out_ref, int64_t out_bstride, EndArgs e) {
+    constexpr int W = 7;
+    constexpr int FL_LD = FL_L + 1, FL_T = FL_L - 2 * FL_H;
+    __shared__ double su[FL_L * FL_LD], sd[FL_L * FL_LD], srp[FL_L * FL_LD], srm[FL_L * FL_LD];
+    __shared__ double sdf[HALFD ? 3 : 1][HALFD ? FL_L * FL_LD : 1];   // HALFD: the forward slots (E, NE, N) of D
+    // The step end is folded in for the 16-patch only (meshes up to 512^2, where a launch counts); the 32-patch runs at
+    // its 64-VGPR limit (two 1024-thread workgroups per CU) and every spilled dword there is 44 MB of scratch traffic
+    // at 2049^2 -- its step end stays a separate tiny launch (femfct_enqueue_tile_flux_limit reports fuse_end back).
+    if (FL_L == 16) step_log_early(e);
+    const int bz = blockIdx.z;
+    const int64_t moff = (int64_t)bz * W * n, voff = (int64_t)bz * n;
+    const TileGeom g = tile_geom<FL_T, FL_H, FL_L>(N);
+    double ui = 0.0, dui = 0.0, mli = 1.0, dfw[3] = {0.0, 0.0, 0.0};
+    if (g.inside) { ui = ulow_[voff + g.i]; dui = du_[voff + g.i]; mli = ml[g.i]; }
+    if (HALFD) {
+        // d_ij is stored once per edge, in the row whose slot towards the neighbour is E, NE or N (k_build_low, half_d)
+        if (g.inside) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s) dfw[s] = D_[moff + (int64_t)(s + 1) * n + g.i];
+        }
+#pragma unroll
+        for (int s = 0; s < 3; ++s) sdf[s][g.self] = dfw[s];
+    }
+    su[g.self] = ui;
+    sd[g.self] = dui;
+    srp[g.self] = 1.0;
+    srm[g.self] = 1.0;
+    __syncthreads();
+    double f[W - 1];
+    // every inside node whose six neighbours are in the patch (or outside the grid) gets its fluxes
+    const bool have = g.inside && g.kvalid >= 1;
+    if (have) {
+        double pp = 0.0, pm = 0.0, umax = ui, umin = ui;
+        const int pc = (GEOM || HALFD) ? mass_edge_counts(g.gx, g.gy, N - 1) : 0;
+        const double mq = (0.5 * h * h) / 12.0;
+#pragma unroll
+        for (int s = 1; s < W; ++s) {
+            const int64_t idx = (int64_t)s * n + g.i;
+            const int nbs = fl_nb<FL_L>(s - 1);
+            const double uj = su[nbs];
+            const double mij = GEOM ? (double)((pc >> (2 * (s - 1))) & 3) * mq : M[idx];
+            double dij;
+            if (HALFD) {
+                // backward slots W, SW, S: the neighbour's forward entry (a neighbour outside the grid has none:
+                // its clamped LDS slot aliases a patch node)
+                const bool exists = ((pc >> (2 * (s - 1))) & 3) != 0;
+                dij = s <= 3 ? sdf[s - 1][g.self] : (exists ? sdf[s - 4][nbs] : 0.0);   // (own entries re-read from LDS: six registers less across the barrier)
+            } else {
+                dij = D_[moff + idx];
+            }
+            const double fs = mij * (dui - sd[nbs]) + dij * (ui - uj);
+            f[s - 1] = fs;
+            pp += fmax(fs, 0.0);
+            pm += fmin(fs, 0.0);
+            // a clamped neighbour (outside the grid) has M = D = 0 and must not enter the bounds:
+            // its LDS slot then aliases a patch node, so take it only when the coefficient is live
+            const bool live = (mij != 0.0) || (dij != 0.0);
+            umax = live ? fmax(umax, uj) : umax;
+            umin = live ? fmin(umin, uj) : umin;
+        }
+        const double qp = umax - ui, qm = umin - ui;
+        srp[g.self] = (pp != 0.0) ? fmin(1.0, mli * qp / (dt * pp)) : 1.0;
+        srm[g.self] = (pm != 0.0) ? fmin(1.0, mli * qm / (dt * pm)) : 1.0;
+    }
+    __syncthreads();
+    if (g.owned) {
+        const double rpi = srp[g.self], rmi = srm[g.self];
+        double fbar = 0.0;
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const double fs = f[s];
+            const int nbs = fl_nb<FL_L>(s);
+            const double a = (fs > 0.0) ? fmin(rpi, srm[nbs]) : fmin(rmi, srp[nbs]);
+            fbar += a * fs;
+        }
+        double* out = const_cast<double*>(vec_ptr(out_ref)) + bz * out_bstride;
+        out[g.i] = ui + dt * fbar / mli;
+    }
+    if (FL_L == 16) step_end_by_last_workgroup(e);
+}
+
+// The last <= 10 Chebyshev iterations of du/dt (helpers.py:175-184) and the whole limiter
+// (helpers.py:1818-1870) in one launch: 8 x 8 tile + halo 12 (ten rings for the iterations, two for
+// the limiter: R+- of the ring-1 neighbours).  du never goes to memory.  Same expressions in the same
+// order as k_tile_cheb + k_tile_flux_limit => bitwise the same step.  Latency regime only.
+template <int GEOM>
+__global__ void __launch_bounds__(STRIP_T)
+k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, const double* __restrict__ b_,
+                       const double* __restrict__ ymid_, const double* __restrict__ yold_, int K, CheOmegas om,
+                       double md_scale, MatRef D_ref, const double* __restrict__ ulow_,
+                       const double* __restrict__ ml, double dt, VecRef out_ref, int64_t out_bstride, EndArgs e) {
+    constexpr int W = 7, HH = 12;
+    __shared__ double ys[3][TILE_L * TILE_LD];
+    __shared__ double su[TILE_L * TILE_LD], srp[TILE_L * TILE_LD], srm[TILE_L * TILE_LD];
+    const int bz = blockIdx.z;
+    const int64_t voff = (int64_t)bz * n;
+    const double* D_ = mat_ptr(D_ref, bz);     // the step's D (one of the pre-built sequence, or the workspace's)
+    const TileGeom g = tile_geom<TILE_L - 2 * HH, HH>(N);
+    double mv[W - 1], dv[W - 1], md = 1.0, rmd = 1.0, bv = 0.0, ym = 0.0, yo = 0.0, ui = 0.0, mli = 1.0;
+#pragma unroll
+    for (int s = 0; s < W - 1; ++s) { mv[s] = 0.0; dv[s] = 0.0; }
+    if (g.inside) {
+        md = M[g.i];
+        rmd = 1.0 / (md_scale * md);
+        if (GEOM) {
+            const int pc = mass_edge_counts(g.gx, g.gy, N - 1);
+            const double mq = (0.5 * h * h) / 12.0;
+#pragma unroll
+            for (int s = 1; s < W; ++s) mv[s - 1] = (double)((pc >> (2 * (s - 1))) & 3) * mq;
+        } else {
+#pragma unroll
+            for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+        }
+        bv = b_[voff + g.i];
+        ym = ymid_[voff + g.i];
+        yo = yold_[voff + g.i];
+        ui = ulow_[voff + g.i];
+        mli = ml[g.i];
+    }
+    ys[0][g.self] = yo;
+    ys[1][g.self] = ym;
+    su[g.self] = ui;
+    srp[g.self] = 1.0;
+    srm[g.self] = 1.0;
+    __syncthreads();
+    step_log_early(e);        // (behind this kernel's own loads; its round trip is covered by the Chebyshev iterations)
+    // D is first needed by the fluxes: requested behind the log copy (which waits for every load in flight) so that a
+    // pre-built D_k, an HBM round trip behind the level counter, is covered by the iterations too
+    if (g.inside) {
+#pragma unroll
+        for (int s = 1; s < W; ++s) dv[s - 1] = D_[(int64_t)s * n + g.i];
+    }
+    int io = 0, im = 1, in_ = 2;
+    for (int k = 0; k < K; ++k) {
+        const double* ymd = ys[im];
+        const double ymv = ymd[g.self];
+        double yn = ymv;
+        if (k < g.kvalid) {
+            double acc = md * ymv;
+#pragma unroll
+            for (int s = 0; s < W - 1; ++s) acc = fma(mv[s], ymd[g.nb[s]], acc);
+            const double z = (bv - acc) * rmd;
+            const double yov = ys[io][g.self];
+            yn = om.w[k] * (z + ymv - yov) + yov;
+        }
+        ys[in_][g.self] = yn;
+        __syncthreads();
+        int t = io; io = im; im = in_; in_ = t;
+    }
+    const double* sd = ys[im];
+    const double dui = sd[g.self];
+    double f[W - 1];
+    // fluxes where all six neighbours carry the final du (one ring inside the iterations' validity)
+    const bool have = g.inside && g.kvalid >= K + 1;
+    if (have) {
+        double pp = 0.0, pm = 0.0, umax = ui, umin = ui;
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const double uj = su[g.nb[s]];
+            const double mij = mv[s], dij = dv[s];
+            const double fs = mij * (dui - sd[g.nb[s]]) + dij * (ui - uj);
+            f[s] = fs;
+            pp += fmax(fs, 0.0);
+            pm += fmin(fs, 0.0);
+            const bool live = (mij != 0.0) || (dij != 0.0);
+            umax = live ? fmax(umax, uj) : umax;
+            umin = live ? fmin(umin, uj) : umin;
+        }
+        const double qp = umax - ui, qm = umin - ui;
+        srp[g.self] = (pp != 0.0) ? fmin(1.0, mli * qp / (dt * pp)) : 1.0;
+        srm[g.self] = (pm != 0.0) ? fmin(1.0, mli * qm / (dt * pm)) : 1.0;
+    }
+    __syncthreads();
+    if (g.owned) {
+        const double rpi = srp[g.self], rmi = srm[g.self];
+        double fbar = 0.0;
+#pragma unroll
+        for (int s = 0; s < W - 1; ++s) {
+            const double fs = f[s];
+            const double a = (fs > 0.0) ? fmin(rpi, srm[g.nb[s]]) : fmin(rmi, srp[g.nb[s]]);
+            fbar += a * fs;
+        }
+        double* out = const_cast<double*>(vec_ptr(out_ref)) + bz * out_bstride;
+        out[g.i] = ui + dt * fbar / mli;
+    }
+    step_end_by_last_workgroup(e);
+}
+
+// du/dt right-hand side + the first Chebyshev iterations in one launch (latency regime):
+//   r = rhs - A u_L (helpers.py:1814), y_1 = w_1 r / Md, then iterations 2..K+1 (helpers.py:175-184).
+// 12 x 12 tile + halo 10: one ring is spent on A u_L, nine on Chebyshev iterations 2..10.
+// Also finalises the low-order solve's bookkeeping (what k_dudt_rhs does in the unfused sequence).
+__global__ void __launch_bounds__(STRIP_T)
+k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride,
+                 const double* __restrict__ M, const double* __restrict__ xa_, const double* __restrict__ xb_,
+                 double* __restrict__ ulow_, double* __restrict__ rdu_, double* __restrict__ omid_,
+                 double* __restrict__ oold_, double* __restrict__ part, StepCtl* __restrict__ ctl_, int budget,
+                 int part_count, int iters_per_unit, double rel_tol, const double* __restrict__ partk, int exact_k,
+                 int K, CheOmegas om, double md_scale, double omega1) {
+    constexpr int W = 7, H = 10;
+    __shared__ double ys[3][TILE_L * TILE_LD];
+    __shared__ double smem[64];
+    const int bz = blockIdx.z;
+    StepCtl* ctl = ctl_ + bz;
+    double* p = part + (int64_t)bz * 4 * FEMFCT_MAX_PARTIALS;
+    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
+    if (exact_k < 0 && blockIdx.y == gridDim.x) {
+        // deferred test: the launch carries one extra row of workgroups; its first one does nothing but reduce the solve's
+        // partials and write the step record (no tile behind it: no workgroup of the kernel ends later for it)
+        if (blockIdx.x == 0)
+            deferred_test_publish(ctl, deferred_test_load(p, partk + (int64_t)bz * 16 * FEMFCT_MAX_PARTIALS, part_count, -exact_k),
+                                  -exact_k, iters_per_unit, rel_tol);
+        return;
+    }
+    // deferred test (exact_k < 0): no launch of the solve set `done`, the iterate is the budget-parity one; nothing below
+    // depends on the test's outcome, only the step log does -- workgroup 0 alone reduces the partials, requested here
+    // and consumed after its own tile, so that nobody waits for them (nor for a look at the control block)
+    const int parity = exact_k < 0 ? (budget & 1) : ctl->done ? ctl->parity : (budget & 1);
+    if (exact_k >= 0)
+        finalize_solve(ctl, p, part_count, budget, iters_per_unit, rel_tol, smem,
+                       partk ? partk + (int64_t)bz * 16 * FEMFCT_MAX_PARTIALS : nullptr, exact_k, wg == 0);
+    const int64_t voff = (int64_t)bz * n;
+    const double* A = mat_ptr(A_ref, bz);
+    const double* x = (parity ? xb_ : xa_) + voff;
+    const double* rhs = vec_ptr(rhs_ref);
+    if (rhs) rhs += bz * rhs_bstride;
+    const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
+    double av[W], mv[W - 1], md = 1.0, rmd = 1.0, ui = 0.0, ri = 0.0;
+#pragma unroll
+    for (int s = 0; s < W; ++s) av[s] = 0.0;
+#pragma unroll
+    for (int s = 0; s < W - 1; ++s) mv[s] = 0.0;
+    if (g.inside) {
+        md = M[g.i];
+        rmd = 1.0 / (md_scale * md);
+#pragma unroll
+        for (int s = 0; s < W; ++s) av[s] = A[(int64_t)s * n + g.i];
+#pragma unroll
+        for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+        ui = x[g.i];
+        ri = rhs ? rhs[g.i] : 0.0;
+    }
+    ys[2][g.self] = ui;
+    __syncthreads();
+    // r = rhs - A u_L on every node whose neighbours are in the patch
+    double r = 0.0, y1 = 0.0;
+    if (g.kvalid >= 1) {
+        double acc = av[0] * ui;
+#pragma unroll
+        for (int s = 1; s < W; ++s) acc = fma(av[s], ys[2][g.nb[s - 1]], acc);
+        r = -acc + ri;
+        y1 = omega1 * (r / (md_scale * md));
+    }
+    __syncthreads();
+    ys[0][g.self] = 0.0;
+    ys[1][g.self] = y1;
+    __syncthreads();
+    int io = 0, im = 1, in_ = 2;
+    for (int k = 0; k < K; ++k) {
+        const double* ymd = ys[im];
+        const double ymv = ymd[g.self];
+        double yn = ymv;
+        if (k + 1 < g.kvalid) {      // one ring already spent on A u_L
+            double acc = md * ymv;
+#pragma unroll
+            for (int s = 0; s < W - 1; ++s) acc = fma(mv[s], ymd[g.nb[s]], acc);
+            const double z = (r - acc) * rmd;
+            const double yov = ys[io][g.self];
+            yn = om.w[k] * (z + ymv - yov) + yov;
+        }
+        ys[in_][g.self] = yn;
+        __syncthreads();
+        int t = io; io = im; im = in_; in_ = t;
+    }
+    if (g.owned) {
+        ulow_[voff + g.i] = ui;
+        rdu_[voff + g.i] = r;
+        omid_[voff + g.i] = ys[im][g.self];
+        if (oold_) oold_[voff + g.i] = ys[io][g.self];
+    }
+}
+
+}  // namespace
+
+// ---- launchers, in the order of a step ---------------------------------------------------------------
+
+// launch 0 with the operator construction fused in (latency regime; needs >= 2 launches in total because
+// ||b|| is reduced by launch 1).  Later launches: femfct_enqueue_tile_jacobi(..., bn_launch = 1, g_build = tiles^2).
+// pre: A is the pre-built L_k sequence (femfct_enqueue_low_seq; Nm must be null), D_k is not stored.
+int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, MatRef A, const double* Nm, int32_t nshared,
+                                     VecRef rhs, int64_t rhs_bstride, VecRef u_n, int64_t u_bstride, double dt,
+                                     int32_t batch, bool pre) {
+    if (pre && Nm) return femfct_fail(ctx, FEMFCT_ERR_INVALID, "pre-built low-order operator with a non-flux matrix");
+    dim3 grid(pl.tiles, pl.tiles, batch);
+    femfct_prof_begin(ctx, KC_JACOBI);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, A, Nm, nshared, rhs, rhs_bstride, u_n,
+                           u_bstride, ctx->d_ml, dt, ctx->d_L, ctx->d_D, ctx->d_b, ctx->d_xb, ctx->d_part, ctx->d_ctl, pl.K);
+    };
+    with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
+        constexpr int H = decltype(h)::value;
+        if (pre) go(k_tile_build_jacobi<H, 1>); else go(k_tile_build_jacobi<H, 0>);
+    });
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
+// L_k and D_k of `entries` consecutive sequence entries of A (k_low_seq); structured mesh in vertex order
+int femfct_enqueue_low_seq(femfct_ctx* ctx, const double* A, double* L, double* D, int32_t entries, double dt) {
+    if (!ctx->implicit_cols || ctx->W != 7 || (int64_t)ctx->N * ctx->N != ctx->n || entries < 1 || entries > 65535)
+        return femfct_fail(ctx, FEMFCT_ERR_INVALID, "low-order sequence: structured mesh in vertex order only");
+    femfct_prof_begin(ctx, KC_ASSEMBLE);
+    hipLaunchKernelGGL(k_low_seq, dim3((ctx->n + 255) / 256, entries), dim3(256), 0, ctx->stream, ctx->n, ctx->N, A, ctx->d_ml,
+                       dt, L, D);
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
+int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double* L, const double* b, double* xa,
+                               double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch, int defer) {
+    const bool big = femfct_tile_big(ctx, pl);
+    double* bigp = big ? ctx->d_bigpart : nullptr;
+    double* pk = ((last || defer) && !big) ? ctx->d_partk : nullptr;
+    dim3 grid(pl.tiles, pl.tiles, batch);
+    femfct_prof_begin(ctx, KC_JACOBI);
+    auto go = [&](auto kernel, int defer_arg) {
+        hipLaunchKernelGGL(kernel, grid, dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, L, b, xa, xb, ctx->d_part, ctx->d_ctl,
+                           launch, pl.K, g_build, ctx->rel_tol, bigp, pk, bn_launch, defer_arg);
+    };
+    if (big) {
+        go(k_tile_jacobi<8, 0, 1>, 0);
+        femfct_launch_reduce_resid(ctx, (int64_t)pl.tiles * pl.tiles, launch, batch);
+    } else {
+        with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
+            constexpr int H = decltype(h)::value;
+            if (pk && !defer) go(k_tile_jacobi<H, 1, 0>, 0); else go(k_tile_jacobi<H, 0, 0>, defer);
+        });
+    }
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
+// the residual maximum of a launch on a grid with more workgroups than in-kernel partials (`count` per batch member);
+// inside the caller's profiling bracket.  Also behind the 64-patch launches (kernels_patch64.hip).
+void femfct_launch_reduce_resid(femfct_ctx* ctx, int64_t count, int launch, int32_t batch) {
+    hipLaunchKernelGGL(k_reduce_resid, dim3(batch), dim3(STRIP_T), 0, ctx->stream, ctx->d_bigpart, count, ctx->d_ctl, launch);
+}
+
+// r, y_1 and Chebyshev iterations 2..(K+1) in one launch, the rest in ceil(.../10) tile launches.
+// tail_first (optional): the caller runs the remaining iterations *tail_first .. iters itself (inputs
+// mid = d_y0, old = d_y2), e.g. fused with the limiter; 0 is stored when nothing remains.
+int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, MatRef A, VecRef rhs, int64_t rhs_bstride, double* ulow,
+                                  int budget_units, int part_count, int iters_per_unit, int exact_k, int iters,
+                                  const double* omegas, double md_scale, int32_t batch, int* tail_first) {
+    constexpr int H = 10;
+    const int T = TILE_L - 2 * H, t = (ctx->N + T - 1) / T;
+    const int K = std::min(iters - 1, H - 1);            // iterations 2..K+1 here
+    CheOmegas om;
+    for (int k = 0; k < K; ++k) om.w[k] = omegas[k + 1];
+    const bool last = (K + 1 == iters);
+    double* omid = last ? ctx->d_du : ctx->d_y0;
+    double* oold = last ? nullptr : ctx->d_y2;
+    femfct_prof_begin(ctx, KC_DUDT_RHS);
+    hipLaunchKernelGGL(k_tile_dudt_cheb, dim3(t, exact_k < 0 ? t + 1 : t, batch), dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, A, rhs,
+                       rhs_bstride, ctx->d_M, ctx->d_xa, ctx->d_xb, ulow, ctx->d_rdu, omid, oold, ctx->d_part, ctx->d_ctl,
+                       budget_units, part_count, iters_per_unit, ctx->rel_tol, exact_k ? ctx->d_partk : nullptr, exact_k,
+                       K, om, md_scale, omegas[0]);
+    femfct_prof_end(ctx);
+    if (tail_first) *tail_first = last ? 0 : K + 2;
+    if (last || tail_first) return FEMFCT_OK;
+    TilePlan tp;
+    tp.H = H; tp.K = H; tp.tiles = t;
+    // remaining iterations K+2 .. iters; inputs (mid, old) = (y0, y2); scratch pair (y1, rp) then (y0, y2)
+    return femfct_enqueue_tile_cheb(ctx, tp, ctx->d_rdu, ctx->d_y0, ctx->d_y2, ctx->d_du, K + 2, iters, omegas, md_scale,
+                                    ctx->d_y1, ctx->d_rp, ctx->d_y0, ctx->d_y2, batch, nullptr);
+}
+
+int femfct_enqueue_tile_cheb(femfct_ctx* ctx, const TilePlan& pl, const double* b, const double* in_mid,
+                             const double* in_old, double* y_out, int k_first, int k_last, const double* omegas,
+                             double md_scale, double* bufA0, double* bufA1, double* bufB0, double* bufB1, int32_t batch,
+                             const ChebIO* io_in) {
+    ChebIO io0{};
+    if (io_in) io0 = *io_in;
+    io0.mid_ref = make_ref(nullptr); io0.mid_bs = 0; io0.out_ref = make_ref(nullptr); io0.out_bs = 0;
+    for_cheb_launches(k_first, k_last, pl.K, omegas, in_mid, in_old, y_out, bufA0, bufA1, bufB0, bufB1,
+                      [&](int k0, int k1, const CheOmegas& om, const double* mid, const double* old, double* omid, double* oold) {
+        femfct_prof_begin(ctx, KC_CHEB);
+        ChebIO io = io0;
+        io.k0 = k0 - 1;
+        if (io_in && k0 == k_first) { io.mid_ref = io_in->mid_ref; io.mid_bs = io_in->mid_bs; }
+        if (io_in && k1 == k_last + 1) { io.out_ref = io_in->out_ref; io.out_bs = io_in->out_bs; }
+        with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
+            hipLaunchKernelGGL((k_tile_cheb<decltype(h)::value>), dim3(pl.tiles, pl.tiles, batch), dim3(STRIP_T), 0, ctx->stream,
+                               ctx->n, ctx->N, ctx->d_M, b, mid, old, omid, oold, k1 - k0, om, md_scale, io);
+        });
+        femfct_prof_end(ctx);
+    });
+    return FEMFCT_OK;
+}
+
+// what a limiter launch that also ends the step hands to step_end.h (level = null: the step end stays its own launch)
+static EndArgs step_end_args(const femfct_ctx* ctx, int32_t batch, bool fuse_end) {
+    EndArgs e{};
+    e.level = nullptr;
+    if (fuse_end) {
+        e.level = ctx->d_level; e.delta = ctx->rep_last ? ctx->end_req_delta * ctx->rep_total : 0;
+        e.ord_adv = ctx->rep_last ? ctx->rep_total : 0; e.ord_off = ctx->ord_bias; e.ctl = ctx->d_ctl; e.log = ctx->d_log;
+        e.kctl = ctx->end_req_krylov ? (const KrylovCtl*)ctx->d_kry_ctl : nullptr; e.klog = (KrylovCtl*)ctx->d_klog;
+        e.batch = batch; e.ticket = ctx->d_ticket;
+    }
+    return e;
+}
+
+int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const double* in_mid, const double* in_old,
+                                        int k_first, int k_last, const double* omegas, double md_scale, MatRef D,
+                                        const double* ulow, double dt, VecRef out, int64_t out_bstride, int32_t batch,
+                                        bool fuse_end) {
+    const int K = k_last - k_first + 1;
+    if (K < 1 || K > 10) return femfct_fail(ctx, FEMFCT_ERR_INVALID, "fused Chebyshev tail: %d iterations", K);
+    const EndArgs e = step_end_args(ctx, batch, fuse_end);
+    CheOmegas om;
+    for (int k = k_first; k <= k_last; ++k) om.w[k - k_first] = omegas[k - 1];
+    const int t = (ctx->N + 7) / 8;
+    femfct_prof_begin(ctx, KC_FLUX);
+    if (femfct_geom_mass(ctx))
+        hipLaunchKernelGGL(k_tile_cheb_flux_limit<1>, dim3(t, t, batch), dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, ctx->h,
+                           ctx->d_M, b, in_mid, in_old, K, om, md_scale, D, ulow, ctx->d_ml, dt, out, out_bstride, e);
+    else
+        hipLaunchKernelGGL(k_tile_cheb_flux_limit<0>, dim3(t, t, batch), dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, ctx->h,
+                           ctx->d_M, b, in_mid, in_old, K, om, md_scale, D, ulow, ctx->d_ml, dt, out, out_bstride, e);
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
+// *fuse_end (in/out): whether this launch also does the step end (only the 16-patch variant can: see the kernel)
+int femfct_enqueue_tile_flux_limit(femfct_ctx* ctx, const double* D, const double* ulow, const double* du, double dt,
+                                   VecRef out, int64_t out_bstride, int32_t batch, bool* fuse_end_io, int half_d) {
+    const bool fuse_end = fuse_end_io && *fuse_end_io && ctx->N <= 512;
+    if (fuse_end_io) *fuse_end_io = fuse_end;
+    const EndArgs e = step_end_args(ctx, batch, fuse_end);
+    femfct_prof_begin(ctx, KC_FLUX);
+    const bool geom = femfct_geom_mass(ctx);
+    auto go = [&](auto kernel, int PL) {       // patch edge PL: tiles of PL - 2 FL_H nodes per side
+        const int t = (ctx->N + PL - 2 * FL_H - 1) / (PL - 2 * FL_H);
+        hipLaunchKernelGGL(kernel, dim3(t, t, batch), dim3(PL * PL), 0, ctx->stream, ctx->n, ctx->N, ctx->h, ctx->d_M, D, ulow, du,
+                           ctx->d_ml, dt, out, out_bstride, e);
+    };
+    with_constant<0, 1>(geom, [&](auto g) {
+        with_constant<0, 1>(half_d != 0, [&](auto hd) {
+            constexpr int G = decltype(g)::value, HD = decltype(hd)::value;
+            if (ctx->N <= 512) go(k_tile_flux_limit<16, G, HD>, 16); else go(k_tile_flux_limit<32, G, HD>, 32);
+        });
+    });
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
+// ---- policy: which of the kernels above run, and how deep their halo is ------------------------------
+
+// the registered mass matrix is the structured mesh's own and may be derived from the cell geometry (FEMFCT_GEOM_MASS)
+bool femfct_geom_mass(const femfct_ctx* ctx) {
+    return ctx->geom_mass && ctx->structured && ctx->mass_is_mesh && ctx->implicit_cols;
+}
+
+// one workgroup per CU is the regime where the fused tail pays (see femfct_tile_plan)
+bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch) {
+    if (!ctx->fuse_flux || ctx->N > 512) return false;
+    const int t = (ctx->N + 7) / 8;
+    return (int64_t)t * t * batch <= ctx->wg_slots;
+}
+
+// The 32 x 32 patch is split as tile + 2 halos with halo H in {8, 9, 10}: H sweeps fit in one launch.
+// Latency regime (small grids): pick the H that needs the fewest launches for the sweep budget
+// (Chebyshev: 19 remaining iterations = 10 + 9 with H = 10).  Bandwidth regime (large grids): H = 8
+// keeps the halo re-reading lowest.  need_partials: the Jacobi variant publishes one residual partial
+// per workgroup, consumed in-kernel up to FEMFCT_MAX_PARTIALS workgroups (else a reduce kernel).
+bool femfct_tile_plan(const femfct_ctx* ctx, TilePlan* pl, bool need_partials, int budget, int batch) {
+    if (!femfct_tiles_usable(ctx)) return false;
+    int H = 8;
+    const bool small = ctx->N <= 512;
+    if (small) {
+        if (budget <= 0) H = 10;
+        else {
+            // fewest launches first, then the smallest halo.  Deep halos (11..13: tiles of 10..6 nodes per
+            // side) only while every workgroup still gets its own CU -- there a launch costs ~4.4 us fixed
+            // + ~0.3 us per sweep whatever the tile size (tools/lat_probe.hip), so 2 x 13 beats 3 x 9.
+            int best = 1 << 30;
+            for (int h = 8; h <= TILE_HMAX; ++h) {
+                const int T = TILE_L - 2 * h, t = (ctx->N + T - 1) / T;
+                if (h > 10 && (!ctx->deep_halo || (int64_t)t * t * batch > ctx->wg_slots)) break;
+                int launches = (budget + h - 1) / h;
+                if (launches < best) { best = launches; H = h; }
+            }
+        }
+    }
+    if (small && ctx->strip_k >= 8 && ctx->strip_k <= TILE_HMAX) H = ctx->strip_k;   // tuning knob (latency regime only)
+    const int T = TILE_L - 2 * H;
+    const int t = (ctx->N + T - 1) / T;
+    if (need_partials && (int64_t)t * t > FEMFCT_MAX_PARTIALS) return false;
+    if (t > 65535) return false;
+    pl->tiles = t;
+    pl->K = H;
+    pl->H = H;
+    return true;
+}
+
+bool femfct_tile_big(const femfct_ctx* ctx, const TilePlan& pl) {
+    return (int64_t)pl.tiles * pl.tiles > FEMFCT_MAX_PARTIALS;
+}
+

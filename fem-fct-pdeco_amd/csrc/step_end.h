@@ -1,5 +1,5 @@
 // End of a time step folded into the step's last kernel, and the geometric mass-matrix counts: shared by the
-// tile kernels (kernels_strip.hip) and the one-workgroup-per-trajectory step kernel (kernels_mesh.hip).
+// tile kernels (kernels_tile32.hip) and the one-workgroup-per-trajectory step kernel (kernels_mesh.hip).
 #pragma once
 
 #include "femfct_internal.h"

@@ -2,7 +2,7 @@
 """Where a kernel's spill code sits: every scratch_load / scratch_store of one kernel in hipcc's ISA listing with the loop
 depth of its basic block (LLVM annotates block labels with `Depth=`).  Usage:
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -S --cuda-device-only -I fem-fct-pdeco_amd/csrc \
-        fem-fct-pdeco_amd/csrc/kernels_strip.hip -o /tmp/ks.s
+        fem-fct-pdeco_amd/csrc/kernels_patch64.hip -o /tmp/ks.s
   python3 tools/scratch_sites.py /tmp/ks.s k_strip_jacobi_pair_walkILi6ELi8E"""
 import re
 import sys
