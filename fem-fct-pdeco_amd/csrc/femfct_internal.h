@@ -7,7 +7,6 @@
 #include <string>
 #include <vector>
 #include <map>
-#include <set>
 #include <tuple>
 
 #include "../../include/femfct.h"
@@ -30,6 +29,29 @@ struct StepCtl {
     double  min_rowsum;   // min_i rowsum(L)
     double  rs[2];        // residual max of fused launch j at [j & 1] when a separate reduce kernel is used
     double  pad;
+};
+
+// Kinds of trajectory sweep.  The numbers appear in graph keys and in the FEMFCT_DEBUG lines: they stay as they are.
+enum SweepKind {
+    SWEEP_SOLIDBODY_FORWARD = 2, SWEEP_SOLIDBODY_ADJOINT = 3,
+    SWEEP_NONLINEAR_FORWARD = 10, SWEEP_NONLINEAR_ADJOINT = 11,
+    SWEEP_SCHNAK_FORWARD = 12, SWEEP_SCHNAK_ADJOINT = 13,
+    SWEEP_CHTXS_FORWARD = 14, SWEEP_CHTXS_ADJOINT = 15,
+    SWEEP_NONLINEAR_ADJOINT_ALLTIME = 16,
+};
+
+// What the sweep controller (sweep_ctl.hip) remembers about one kind of sweep: the forward and the adjoint operator of a
+// problem need different sweep counts, and shared budgets would make them evict each other.
+struct SweepKindState {
+    int budget = 48;        // Jacobi sweeps (BiCGStab iterations once low_bicg) the next sweep enqueues per step
+    int good = 0;           // last Jacobi budget that sufficed (0: none yet)
+    int fail = 0;           // largest Jacobi budget known to be too small (0: none yet)
+    int mesh_cap = 0;       // sweep cap of the one-workgroup step; 0: unset, min(max_iters, 96) at the kind's first such sweep
+    int cheb_budget = 40;   // species solve: Chebyshev iterations per step ...
+    int bicg_budget = 40;   // ... and BiCGStab iterations per step (separate: the two converge at different rates)
+    bool full_rows = false; // full-row Jacobi kernels: asked for by the driver, or FEMFCT_FLAG_ROW_PAIRS was raised
+    bool low_bicg = false;  // the Jacobi iteration did not contract: low-order solve by BiCGStab from then on
+    bool cheb_off = false;  // the Chebyshev iteration did not contract: species solve by BiCGStab from then on
 };
 
 struct femfct_ctx {
@@ -60,14 +82,10 @@ struct femfct_ctx {
     // solver settings
     int solver = FEMFCT_SOLVER_JACOBI;       // low-order solver of the sweep in progress
     int solver_user = FEMFCT_SOLVER_JACOBI;  // what femfct_set_solver asked for
-    std::set<int> kind_low_bicg;             // sweep kinds whose Jacobi iteration did not contract: BiCGStab from then on
     double rel_tol = 1e-13;
     int max_iters = 400;
     int sweep_budget = 48;      // adaptive: sweeps enqueued per step (stand-alone femfct_fct_step)
-    std::map<int, int> kind_good;   // last Jacobi budget that sufficed, per kind
-    std::map<int, int> kind_fail;   // largest Jacobi budget known to be too small, per kind
-    std::map<int, int> kind_mesh_budget;   // sweep cap of the one-workgroup step, per kind (fixed unless it proved too small)
-    std::map<int, int> kind_budget, kind_kbudget;   // per trajectory kind (forward/adjoint of each system)
+    std::map<int, SweepKindState> kinds;     // what the sweep controller remembers, per SweepKind (sweep_ctl.hip)
     bool use_graphs = true;
     // hipGraph replay is held back while a rocprofiler-sdk tool intercepts the HSA queues (rocprofv3 --kernel-trace /
     // --pmc): ROCm 7.2.0's interceptor walks a graph launch's AQL packet batch past the end of the 16384-packet ring when
@@ -100,8 +118,7 @@ struct femfct_ctx {
     unsigned long long* d_pair_trace = nullptr;   // FEMFCT_PAIR_TRACE=<file>: phase timestamps of the pair walkers, dumped at destroy
     int pair_prio = 0, pair_split = 50;   // FEMFCT_PAIR_PRIO / FEMFCT_PAIR_SPLIT: balance between the two workgroups of a CU (k_strip_jacobi_pair_walk)
     int pair_shape = 5;         // FEMFCT_PAIR_SHAPE: 5 = 6 rows x 8 waves (the product's), 3 = 8 x 8, 4 = 7 x 8, 6 = 12 x 4 (measurement)
-    bool pair_rows = false;     // set by femfct_run_sweep for the sweep in progress: its kind has only shown upwind rows so far
-    std::set<int> kind_fullrows;    // sweep kinds that raised FEMFCT_FLAG_ROW_PAIRS: full-row kernels from then on
+    bool pair_rows = false;     // set by femfct_sweep_plan for the sweep in progress: its kind has only shown upwind rows so far
     // one workgroup = one trajectory (kernels_mesh.hip): the whole step of a small mesh (N <= 42) in one launch
     bool mesh_step = true;          // FEMFCT_MESH_STEP
     int mesh_step_min_batch = 1;    // FEMFCT_MESH_STEP_BATCH: trajectories per launch from which it replaces the tile path
@@ -196,7 +213,6 @@ struct femfct_ctx {
     int kry_budget = 40;            // adaptive
     void* d_klog = nullptr;         // KrylovCtl[tr_steps * tr_batch]
     int species_solver = 0;         // 0: Chebyshev where the tile plan applies (fallback BiCGStab), 1: BiCGStab
-    std::set<int> kind_cheb_off;    // sweep kinds whose Chebyshev iteration failed to contract
     double* d_chs_om = nullptr;     // [kry_batch][chs_om_cap] omega tables
     double* d_chs_scale = nullptr;  // [kry_batch] (lmin+lmax)/2
     int chs_om_cap = 0;
@@ -240,6 +256,11 @@ int femfct_ensure_krylov_ws(femfct_ctx* ctx, int32_t batch);
 void femfct_drop_graphs(femfct_ctx* ctx);
 void femfct_release_pattern(femfct_ctx* ctx);
 int femfct_round_budget(const femfct_ctx* ctx, int b);
+#define FEMFCT_INTERNAL __attribute__((visibility("hidden")))     // not exported from the shared library
+// what the setters make the sweep controller forget (sweep_ctl.hip: which fields survive which setter)
+FEMFCT_INTERNAL void femfct_forget_jacobi_budgets(femfct_ctx* ctx);       // femfct_set_solver, femfct_set_fusion
+FEMFCT_INTERNAL void femfct_forget_bicgstab_handovers(femfct_ctx* ctx);   // femfct_set_solver
+FEMFCT_INTERNAL void femfct_forget_cheb_off(femfct_ctx* ctx);             // femfct_set_species_solver
 
 // graph-key helpers
 static inline uint64_t key_bits(const void* p) { return (uint64_t)(uintptr_t)p; }

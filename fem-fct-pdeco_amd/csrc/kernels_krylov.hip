@@ -447,7 +447,8 @@ static double element_lambda_min(double h, double tau) {
 }
 
 bool femfct_species_cheb(const femfct_ctx* ctx, int kind) {
-    if (ctx->species_solver != 0 || ctx->kind_cheb_off.count(kind)) return false;
+    const auto st = ctx->kinds.find(kind);
+    if (ctx->species_solver != 0 || (st != ctx->kinds.end() && st->second.cheb_off)) return false;
     if (ctx->structured && femfct_mesh_solve_fits(ctx)) return true;     // one workgroup per system (any ordering)
     if (!femfct_tiles_usable(ctx)) return false;
     TilePlan tp;

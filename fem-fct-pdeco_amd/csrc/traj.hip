@@ -206,7 +206,7 @@ int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const 
         return FEMFCT_OK;
     };
     auto step = [&](int budget, int, int reps) {
-        femfct_ctx::GraphKey key{(uint64_t)2, key_bits(Arot), key_bits(c_traj), key_bits(c_shared), key_bits(u_traj),
+        femfct_ctx::GraphKey key{(uint64_t)SWEEP_SOLIDBODY_FORWARD, key_bits(Arot), key_bits(c_traj), key_bits(c_shared), key_bits(u_traj),
                                  key_bits(num_steps), key_bits(dt), key_bits(eps), key_bits(rot_scale), key_bits(bx),
                                  key_bits(by), key_bits(batch), key_bits((int32_t)budget), key_bits(ctx->rel_tol),
                                  key_bits(pre ? Aall.base : nullptr), key_bits(src_traj), key_bits((int32_t)inl),
@@ -237,8 +237,7 @@ int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const 
         });
     };
     // (a diffusive operator has no upwind rows: no point in finding that out from a whole sweep with the pair-compact launch)
-    if (eps != 0.0) ctx->kind_fullrows.insert(2);
-    return femfct_run_sweep(ctx, 2, num_steps, batch, 0, false, begin, step);
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SOLIDBODY_FORWARD, num_steps, batch, 0, false, eps != 0.0}, begin, step);
 }
 
 int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
@@ -275,7 +274,7 @@ int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const doub
         return FEMFCT_OK;
     };
     auto step = [&](int budget, int, int reps) {
-        femfct_ctx::GraphKey key{(uint64_t)3, key_bits(Arot), key_bits(c_traj), key_bits(c_shared), key_bits(u_traj),
+        femfct_ctx::GraphKey key{(uint64_t)SWEEP_SOLIDBODY_ADJOINT, key_bits(Arot), key_bits(c_traj), key_bits(c_shared), key_bits(u_traj),
                                  key_bits(uhat), key_bits(p_traj), key_bits(num_steps), key_bits(dt), key_bits(eps),
                                  key_bits(rot_scale), key_bits(bx), key_bits(by), key_bits(alltime), key_bits(batch),
                                  key_bits((int32_t)budget), key_bits(ctx->rel_tol), key_bits(pre ? Aall.base : nullptr),
@@ -305,8 +304,7 @@ int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const doub
             return FEMFCT_OK;
         });
     };
-    if (eps != 0.0) ctx->kind_fullrows.insert(3);
-    return femfct_run_sweep(ctx, 3, num_steps, batch, num_steps - 1, false, begin, step);
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SOLIDBODY_ADJOINT, num_steps, batch, num_steps - 1, false, eps != 0.0}, begin, step);
 }
 
 // per-step solver diagnostics of the most recent trajectory sweep: info[step*batch + b]

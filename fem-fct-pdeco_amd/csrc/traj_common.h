@@ -66,177 +66,63 @@ static inline VecRef lref(const femfct_ctx* ctx, const double* p, const int32_t*
     return make_ref(p, level, stride, off + (level ? ctx->level_bias : 0));
 }
 
-// Replays `step(jacobi_budget, krylov_budget, reps)` until num_steps are done, then inspects the per-step solver
-// logs; if a sweep/iteration budget was too small anywhere the whole sweep is repeated with a
+// ---- the sweep controller (sweep_ctl.hip): plan -> run -> verdict, repeated until the sweep is accepted or fails ----
+struct SweepSpec {
+    SweepKind kind;
+    int32_t num_steps, batch;
+    int level0;         // time level the device counter starts from
+    bool krylov;        // the step has a species solve (its log is read too)
+    bool full_rows;     // the kind starts on the full-row Jacobi kernels (diffusion / reaction terms: no upwind rows)
+};
+struct SweepPlan {
+    int budget, kbudget;    // what `step` enqueues: Jacobi sweeps and species-solve iterations per step
+    bool meshp, cheb;       // one-workgroup step; Chebyshev species solve
+};
+enum { FEMFCT_SWEEP_REPEAT = -1 };  // verdict: neither accepted (FEMFCT_OK) nor failed (FEMFCT_ERR_*, all positive)
+// sets ctx->pair_rows / ctx->solver for the attempt and picks its budgets from the kind's record
+FEMFCT_INTERNAL int femfct_sweep_plan(femfct_ctx* ctx, const SweepSpec& sp, SweepPlan* plan);
+// copies the step logs of the sweep just enqueued into h_log / h_klog and waits for them
+FEMFCT_INTERNAL int femfct_sweep_fetch_logs(femfct_ctx* ctx, const SweepSpec& sp);
+// reads the logs, updates the kind's record: FEMFCT_OK, FEMFCT_SWEEP_REPEAT or an error (femfct_fail)
+FEMFCT_INTERNAL int femfct_sweep_verdict(femfct_ctx* ctx, const SweepSpec& sp, const SweepPlan& plan);
+FEMFCT_INTERNAL void femfct_sweep_report_times(const SweepSpec& sp, const double t[4]);   // FEMFCT_DEBUG_TIMES=<ms>
+
+// species-solve budget after a sweep whose worst step took `worst` iterations
+// (Chebyshev reports the count that meets tol/10 at its asymptotic rate: no extra margin)
+static inline int femfct_next_kry_budget(const femfct_ctx* ctx, int worst, bool cheb) {
+    return std::min(ctx->kry_max_iters, cheb ? std::max(8, worst + 1) : std::max(8, worst + worst / 4 + 2));
+}
+
+// Replays `step(jacobi_budget, krylov_budget, reps)` until num_steps are done, then has the per-step solver logs
+// inspected; if a sweep/iteration budget was too small anywhere the whole sweep is repeated with a
 // larger one (the sweep's inputs are never overwritten, so a repeat is exact).
 template <class Begin, class Step>
-int femfct_run_sweep(femfct_ctx* ctx, int kind, int32_t num_steps, int32_t batch, int level0, bool krylov,
-                     Begin&& begin, Step&& step) {
-    // budgets are remembered per kind of sweep: the forward and the adjoint operator of a problem
-    // need different sweep counts, and a shared budget would make them evict each other
-    if (!ctx->kind_budget.count(kind)) ctx->kind_budget[kind] = 48;
+int femfct_run_sweep(femfct_ctx* ctx, const SweepSpec& sp, Begin&& begin, Step&& step) {
     struct RestoreSolver {       // the effective solver is per kind of sweep; the user's choice comes back on every exit
         femfct_ctx* c;
         ~RestoreSolver() { c->solver = c->solver_user; c->pair_rows = false; }
     } restore_solver{ctx};
+    const bool dbg_t = getenv("FEMFCT_DEBUG_TIMES") != nullptr;
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     for (;;) {
-        // bandwidth regime: rows of an upwind operator as one value per opposing pair (k_strip_jacobi_pair_walk), until a
-        // sweep of this kind shows a row that is not one (FEMFCT_FLAG_ROW_PAIRS below)
-        ctx->pair_rows = !ctx->kind_fullrows.count(kind);
-        // a kind whose operator lies outside the scheme's dt restriction (Jacobi does not contract: the reference's
-        // spsolve does not care, helpers.py:1782) is solved with Jacobi-preconditioned BiCGStab from then on
-        ctx->solver = ctx->kind_low_bicg.count(kind) ? FEMFCT_SOLVER_BICGSTAB : ctx->solver_user;
-        if (ctx->solver == FEMFCT_SOLVER_BICGSTAB) {
-            int rk = femfct_ensure_krylov_ws(ctx, batch);
-            if (rk != FEMFCT_OK) return rk;
-        }
-        // species solves: Chebyshev (structured mesh) and BiCGStab keep separate iteration budgets
-        const bool cheb = krylov && femfct_species_cheb(ctx, kind);
-        const int kkey = cheb ? kind : kind + 1000;
-        if (!ctx->kind_kbudget.count(kkey)) ctx->kind_kbudget[kkey] = 40;
-        // the one-workgroup step (kernels_mesh.hip) stops by itself: its budget is only a cap, kept fixed so that every sweep
-        // of the kind replays the same captured graphs (a budget that follows the iteration counts would re-capture them)
-        const bool meshp = femfct_mesh_step_wanted(ctx, batch);
-        if (meshp && !ctx->kind_mesh_budget.count(kind)) ctx->kind_mesh_budget[kind] = std::min(ctx->max_iters, 96);
-        const int budget = meshp ? ctx->kind_mesh_budget[kind] : femfct_round_budget(ctx, ctx->kind_budget[kind]);
-        const int kbudget = femfct_round_kry_budget(ctx, ctx->kind_kbudget[kkey]);
-        const bool dbg_t = getenv("FEMFCT_DEBUG_TIMES") != nullptr;
-        auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double tt0 = dbg_t ? now() : 0.0;
-        int rc = begin();
+        SweepPlan plan;
+        int rc = femfct_sweep_plan(ctx, sp, &plan);
         if (rc != FEMFCT_OK) return rc;
-        const double tt1 = dbg_t ? now() : 0.0;
-        int32_t init[2] = {level0, 0};
+        double t[4] = {dbg_t ? now() : 0.0, 0.0, 0.0, 0.0};
+        if ((rc = begin()) != FEMFCT_OK) return rc;
+        if (dbg_t) t[1] = now();
+        int32_t init[2] = {sp.level0, 0};
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_level, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
         // several identical time steps per captured graph: fewer graph launches, no inter-graph gaps
-        const int32_t per_graph = std::max(1, std::min(ctx->steps_per_graph, num_steps));
-        for (int32_t k = 0; k < num_steps; k += per_graph) {
-            rc = step(budget, kbudget, std::min(per_graph, num_steps - k));
+        const int32_t per_graph = std::max(1, std::min(ctx->steps_per_graph, sp.num_steps));
+        for (int32_t k = 0; k < sp.num_steps; k += per_graph) {
+            rc = step(plan.budget, plan.kbudget, std::min(per_graph, sp.num_steps - k));
             if (rc != FEMFCT_OK) return rc;
         }
-        const double tt2 = dbg_t ? now() : 0.0;
-        ctx->log_steps = ctx->log_batch = 0;      // no matching log while the copies are in flight / after a failure
-        ctx->h_log.resize((size_t)num_steps * batch);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_log.data(), ctx->d_log, sizeof(StepCtl) * ctx->h_log.size(),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        if (krylov) {
-            ctx->h_klog.resize(sizeof(KrylovCtl) * (size_t)num_steps * batch);
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_klog.data(), ctx->d_klog, ctx->h_klog.size(), hipMemcpyDeviceToHost,
-                                        ctx->stream));
-        } else {
-            ctx->h_klog.clear();
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (dbg_t) {
-            const double tt3 = now();
-            if (tt3 - tt0 > atof(getenv("FEMFCT_DEBUG_TIMES")))      // FEMFCT_DEBUG_TIMES=<ms>: report sweeps that take longer
-                fprintf(stderr, "[femfct] sweep kind %d took %.1f ms: begin %.2f, enqueue %.2f, wait %.2f\n", kind, tt3 - tt0, tt1 - tt0, tt2 - tt1, tt3 - tt2);
-        }
-        ctx->log_steps = num_steps;
-        ctx->log_batch = batch;
-        int worst = 0, kworst = 0;
-        bool short_budget = false, kshort = false, coarse = false, not_pairs = false;
-        double worst_res = 0.0, kworst_res = 0.0;
-        for (const StepCtl& c : ctx->h_log) not_pairs = not_pairs || (c.flags & FEMFCT_FLAG_ROW_PAIRS);
-        if (not_pairs) {             // what the pair-compact launches computed is void: repeat with the full-row kernels
-            if (getenv("FEMFCT_DEBUG")) fprintf(stderr, "[femfct] sweep kind %d: rows with both entries of a pair -> full-row Jacobi launches\n", kind);
-            ctx->kind_fullrows.insert(kind);
-            ctx->log_steps = ctx->log_batch = 0;
-            continue;
-        }
-        for (const StepCtl& c : ctx->h_log) {
-            if (c.iters > worst) coarse = (c.flags & FEMFCT_FLAG_COARSE_ITERS) != 0;
-            worst = std::max(worst, c.iters);
-            if (c.flags & FEMFCT_FLAG_SOLVER_BUDGET) {
-                short_budget = true;
-                worst_res = (c.resid == c.resid) ? std::max(worst_res, c.resid) : INFINITY;   // NaN: diverged
-            }
-        }
-        if (krylov) {
-            const KrylovCtl* kl = (const KrylovCtl*)ctx->h_klog.data();
-            for (size_t k = 0; k < (size_t)num_steps * batch; ++k) {
-                kworst = std::max(kworst, kl[k].iters);
-                if ((kl[k].flags & FEMFCT_FLAG_SOLVER_BUDGET) || !(kl[k].resid == kl[k].resid)) {
-                    kshort = true;
-                    kworst_res = std::max(kworst_res, kl[k].resid == kl[k].resid ? kl[k].resid : INFINITY);   // NaN: diverged
-                }
-            }
-        }
-        if (getenv("FEMFCT_DEBUG"))
-            fprintf(stderr, "[femfct] sweep kind %d: budget %d (krylov %d) worst %d kworst %d short %d/%d, %d graphs captured so far (%zu cached)\n",
-                    kind, budget, kbudget, worst, kworst, (int)short_budget, (int)kshort, ctx->graph_captures, ctx->graphs.size());
-        if (!short_budget && !kshort && meshp) {
-            if (krylov)
-                ctx->kind_kbudget[kkey] = std::min(ctx->kry_max_iters, cheb ? std::max(8, kworst + 1)
-                                                                             : std::max(8, kworst + kworst / 4 + 2));
-            return FEMFCT_OK;
-        }
-        if (short_budget && meshp && budget < ctx->max_iters && worst_res < 1.0) {
-            ctx->kind_mesh_budget[kind] = std::min(ctx->max_iters, 2 * budget);
-            short_budget = false;
-            if (!kshort) continue;
-        }
-        if (!short_budget && !kshort) {
-            ctx->kind_good[kind] = budget;
-            ctx->kind_budget[kind] = femfct_next_budget(ctx, worst, coarse);
-            // whole-mesh workgroups stop by themselves: the budget is only an upper bound, keep a margin
-            const bool single = femfct_tile4_wanted(ctx, batch) && femfct_single_patch(ctx, batch);
-            if (single) ctx->kind_budget[kind] = std::min(ctx->max_iters, worst + 6);
-            // Tiles report whole launches: `worst` = U launches of K sweeps, and every step was still above
-            // the tolerance after (U-1)*K.  If one launch fewer of the deepest halo could cover that, try it
-            // once (a failure is remembered per kind and costs one repeated sweep).
-            int K = 0, U = 0, K2 = 0, U2 = 0;
-            if (!single && femfct_jacobi_plan(ctx, budget, batch, &K, &U) && worst > 0) {
-                U = (worst + K - 1) / K;
-                const int lb = (U - 1) * K;
-                int top = 0;
-                for (int b_try = lb + 1; U >= 2 && b_try < worst; ++b_try)
-                    if (femfct_jacobi_plan(ctx, b_try, batch, &K2, &U2) && U2 <= U - 1) top = b_try;
-                const int known_fail = ctx->kind_fail.count(kind) ? ctx->kind_fail[kind] : 0;
-                if (top > lb && top > known_fail && 10 * top >= 7 * worst) ctx->kind_budget[kind] = top;
-            }
-            // (Chebyshev reports the count that meets tol/10 at its asymptotic rate: no extra margin)
-            if (krylov)
-                ctx->kind_kbudget[kkey] = std::min(ctx->kry_max_iters, cheb ? std::max(8, kworst + 1)
-                                                                             : std::max(8, kworst + kworst / 4 + 2));
-            return FEMFCT_OK;
-        }
-        if (short_budget) {
-            ctx->kind_fail[kind] = std::max(ctx->kind_fail.count(kind) ? ctx->kind_fail[kind] : 0, budget);
-            // no contraction at all (residual not below ||b|| after a whole budget, or not a number), or the sweep cap
-            // reached: hand this kind of sweep to BiCGStab and repeat it
-            const bool hopeless = !(worst_res < 1.0) || budget >= ctx->max_iters;
-            if (hopeless && ctx->solver == FEMFCT_SOLVER_JACOBI) {
-                if (getenv("FEMFCT_DEBUG"))
-                    fprintf(stderr, "[femfct] sweep kind %d: Jacobi residual %.3e after %d sweeps -> BiCGStab\n", kind,
-                            worst_res, budget);
-                ctx->kind_low_bicg.insert(kind);
-                ctx->kind_budget[kind] = 40;
-                ctx->kind_fail.erase(kind);
-                ctx->kind_good.erase(kind);
-                femfct_drop_graphs(ctx);
-                continue;
-            }
-            // a residual that is not finite (NaN or Inf in the data) stays so whatever the budget: fail now
-            if (budget >= ctx->max_iters || !(worst_res < INFINITY))
-                return femfct_fail(ctx, FEMFCT_ERR_NOT_CONVERGED,
-                                   "low-order solve: residual %.3e after %d %s (tol %.1e)", worst_res, budget,
-                                   ctx->solver == FEMFCT_SOLVER_BICGSTAB ? "BiCGStab iterations" : "Jacobi sweeps",
-                                   ctx->rel_tol);
-            // a failed attempt at fewer launches goes back to the budget that worked
-            const int good = ctx->kind_good.count(kind) ? ctx->kind_good[kind] : 0;
-            ctx->kind_budget[kind] = good > budget ? good : femfct_grow_budget(ctx, budget);
-        }
-        if (kshort && cheb) {
-            // not contracting (complex spectrum outside the assumed interval) or out of budget: BiCGStab
-            if (!(kworst_res < 10.0) || kbudget >= ctx->kry_max_iters) ctx->kind_cheb_off.insert(kind);
-            else ctx->kind_kbudget[kkey] = std::min(ctx->kry_max_iters, std::max(kbudget + 10, kworst + kworst / 10 + 5));
-        } else if (kshort) {
-            if (kbudget >= ctx->kry_max_iters || !(kworst_res < INFINITY))
-                return femfct_fail(ctx, FEMFCT_ERR_NOT_CONVERGED,
-                                   "BiCGStab: residual %.3e after %d iterations (tol %.1e)", kworst_res, kbudget,
-                                   ctx->kry_tol);
-            ctx->kind_kbudget[kkey] = std::min(ctx->kry_max_iters, kbudget * 2);
-        }
+        if (dbg_t) t[2] = now();
+        if ((rc = femfct_sweep_fetch_logs(ctx, sp)) != FEMFCT_OK) return rc;
+        if (dbg_t) { t[3] = now(); femfct_sweep_report_times(sp, t); }
+        rc = femfct_sweep_verdict(ctx, sp, plan);
+        if (rc != FEMFCT_SWEEP_REPEAT) return rc;
     }
 }

@@ -72,7 +72,7 @@ struct Lv {  // VecRef factory bound to the ctx level counter (and to the step o
 // 950-951, 1332-1333): one level, n doubles per batch member, for every step.  Per step (the *_ct entry points, as in the
 // all-time scripts, e.g. Schnak_FCT_PDECO_alltime.py:182-191): a trajectory of num_steps+1 levels per member, and the step
 // from level n to n+1 reads level n+1.  Graph keys: the per-step steps carry their own tag (kind + 100) and c_shared, so
-// they never meet a frozen key; the sweep kind (budgets, kind_fullrows, ...) is shared with the frozen call, the operators
+// they never meet a frozen key; the sweep kind (budgets, full rows, ...) is shared with the frozen call, the operators
 // being the same.
 struct Ctl {
     const double* base;
@@ -142,7 +142,7 @@ int femfct_set_krylov(femfct_ctx* ctx, double rel_tol, int32_t max_iters) {
 int femfct_set_species_solver(femfct_ctx* ctx, int32_t mode) {
     ARG_TRY(ctx, ctx && (mode == FEMFCT_SPECIES_AUTO || mode == FEMFCT_SPECIES_BICGSTAB), "unknown species solver");
     ctx->species_solver = mode;
-    ctx->kind_cheb_off.clear();
+    femfct_forget_cheb_off(ctx);
     return FEMFCT_OK;
 }
 
@@ -177,7 +177,7 @@ int femfct_bicgstab(femfct_ctx* ctx, const double* mat_ell, int32_t mat_shared, 
             }
         }
         if (!bad) {
-            ctx->kry_budget = std::min(ctx->kry_max_iters, std::max(8, worst + worst / 4 + 2));
+            ctx->kry_budget = femfct_next_kry_budget(ctx, worst, false);
             return FEMFCT_OK;
         }
         // (a residual that is not finite stays so whatever the budget)
@@ -211,7 +211,7 @@ static int nonlinear_forward(femfct_ctx* ctx, const double* Aw_ell, Ctl c, doubl
         return c.per_step ? (int)FEMFCT_OK : femfct_enqueue_load(ctx, load(), ctx->d_trRhs, batch);
     };
     auto step = [&](int budget, int, int reps) {
-        auto key = KEY(c.tag(10), key_bits(Aw_ell), key_bits(c.base), key_bits(u_traj), key_bits(num_steps),
+        auto key = KEY(c.tag(SWEEP_NONLINEAR_FORWARD), key_bits(Aw_ell), key_bits(c.base), key_bits(u_traj), key_bits(num_steps),
                        key_bits(dt), key_bits(eps), key_bits(batch), key_bits((int32_t)budget), key_bits(ctx->rel_tol));
         c.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
@@ -233,8 +233,8 @@ static int nonlinear_forward(femfct_ctx* ctx, const double* Aw_ell, Ctl c, doubl
             return femfct_enqueue_step_end(ctx, 1, batch, false);
         });
     };
-    ctx->kind_fullrows.insert(10);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
-    return femfct_run_sweep(ctx, 10, num_steps, batch, 0, false, begin, step);
+    // (diffusion / reaction terms: rows with both entries of a pair from the start: full rows)
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_NONLINEAR_FORWARD, num_steps, batch, 0, false, true}, begin, step);
 }
 
 // c_level = the control level the reference freezes for the whole sweep (level 1: helpers.py:950-951), n doubles per member
@@ -254,8 +254,8 @@ int femfct_nonlinear_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const dou
 // helpers.py:968-1038: p(T) = uhat_T - u(T); FCT_alg_ref(-Mat_p, 0, p_{n+1}, non_flux_mat = M_u2(u_n) - M).
 // alltime (nonlinear_FCT_PDECO_alltime.py:198-216 with the HEAD operators): uhat is a trajectory (batch stride ts, or 0 when
 // uhat_shared), p(T) = 0 and the step to level n carries rhs = M (uhat_n - u_n) (FCT_alg_ref scales rhs by dt itself,
-// helpers.py:1780).  The all-time sweep is a kind of its own (16): its graphs never meet a final-time key, and its
-// budgets leave those of the final-time sweep (kind 11) as they were.  Both launch the same kernels per step.
+// helpers.py:1780).  The all-time sweep is a kind of its own (SWEEP_NONLINEAR_ADJOINT_ALLTIME): its graphs never meet a final-time key, and its
+// budgets leave those of the final-time sweep as they were.  Both launch the same kernels per step.
 static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat,
                              int32_t uhat_shared, bool alltime, double* p_traj, int32_t num_steps, double dt, double eps,
                              int32_t batch) {
@@ -264,7 +264,7 @@ static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double
     ARG_TRY(ctx, Aw_ell && u_traj && uhat && p_traj, "null argument");
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     const int64_t n = ctx->n, wn = (int64_t)ctx->W * n, ts = (int64_t)(num_steps + 1) * n;
-    const int kind = alltime ? 16 : 11;
+    const SweepKind kind = alltime ? SWEEP_NONLINEAR_ADJOINT_ALLTIME : SWEEP_NONLINEAR_ADJOINT;
     const int32_t shared = uhat_shared ? 1 : 0;
     Lv L{ctx, ctx->d_level, n};
     auto begin = [&]() {
@@ -306,8 +306,8 @@ static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double
             return femfct_enqueue_step_end(ctx, -1, batch, false);
         });
     };
-    ctx->kind_fullrows.insert(kind);    // (diffusion / reaction terms: rows with both entries of a pair from the start)
-    return femfct_run_sweep(ctx, kind, num_steps, batch, num_steps - 1, false, begin, step);
+    // (diffusion / reaction terms: rows with both entries of a pair from the start: full rows)
+    return femfct_run_sweep(ctx, SweepSpec{kind, num_steps, batch, num_steps - 1, false, true}, begin, step);
 }
 
 int femfct_nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat_T,
@@ -388,11 +388,11 @@ static int schnak_forward(femfct_ctx* ctx, const double* Aw_ell, const double* w
         return wsc ? (int)FEMFCT_OK : wind_ops(0);
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY(c.tag(12), key_bits(Aw_ell), key_bits(c.base), key_bits(u_traj), key_bits(v_traj),
+        auto key = KEY(c.tag(SWEEP_SCHNAK_FORWARD), key_bits(Aw_ell), key_bits(c.base), key_bits(u_traj), key_bits(v_traj),
                        key_bits(num_steps), key_bits(dt), key_bits(Du), key_bits(Dv), key_bits(c_b), key_bits(gam),
                        key_bits(om1), key_bits(om2), key_bits(rescaling), key_bits(batch), key_bits((int32_t)budget),
                        key_bits((int32_t)kbudget), key_bits(ctx->rel_tol), key_bits(ctx->kry_tol),
-                       key_bits((int32_t)femfct_species_cheb(ctx, 12)), key_bits(wsc));
+                       key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_SCHNAK_FORWARD)), key_bits(wsc));
         c.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
             if (wsc) wind_ops(1);       // wind.t = t_{n+1} (helpers.py:565-566)
@@ -415,13 +415,13 @@ static int schnak_forward(femfct_ctx* ctx, const double* Aw_ell, const double* w
             ws.f1 = L(u_traj, 1); ws.f2 = L(u_traj, 1); ws.f1_bs = ws.f2_bs = ts;
             femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trMat, batch);
             femfct_request_fused_end(ctx, 1, true);       // (the one-launch species solve logs and advances itself)
-            r = femfct_enqueue_species_solve(ctx, 12, ctx->d_trMat, 0, ctx->d_trRhs2, L(v_traj, 0), ts, L(v_traj, 1), ts, batch, kbudget, dt * Dv);
+            r = femfct_enqueue_species_solve(ctx, SWEEP_SCHNAK_FORWARD, ctx->d_trMat, 0, ctx->d_trRhs2, L(v_traj, 0), ts, L(v_traj, 1), ts, batch, kbudget, dt * Dv);
             if (r != FEMFCT_OK) return r;
             return femfct_enqueue_step_end(ctx, 1, batch, true);
         });
     };
-    ctx->kind_fullrows.insert(12);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
-    return femfct_run_sweep(ctx, 12, num_steps, batch, 0, true, begin, step);
+    // (diffusion / reaction terms: rows with both entries of a pair from the start: full rows)
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SCHNAK_FORWARD, num_steps, batch, 0, true, true}, begin, step);
 }
 
 // helpers.py:599-698.  AwT_ell = assemble_sparse(dot(wind,grad(u))*w*dx) = transpose of Aw.
@@ -477,11 +477,11 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
         return terminal_diff(ctx, vhat_T, v_traj, q_traj, num_steps, batch);
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY((uint64_t)13, key_bits(AwT_ell), key_bits(u_traj), key_bits(v_traj), key_bits(uhat_T),
+        auto key = KEY((uint64_t)SWEEP_SCHNAK_ADJOINT, key_bits(AwT_ell), key_bits(u_traj), key_bits(v_traj), key_bits(uhat_T),
                        key_bits(vhat_T), key_bits(p_traj), key_bits(q_traj), key_bits(num_steps), key_bits(dt),
                        key_bits(Du), key_bits(Dv), key_bits(gam), key_bits(om1), key_bits(om2), key_bits(batch),
                        key_bits(alltime), key_bits((int32_t)budget), key_bits((int32_t)kbudget), key_bits(ctx->rel_tol), key_bits(ctx->kry_tol),
-                       key_bits((int32_t)femfct_species_cheb(ctx, 13)), key_bits(wsc));
+                       key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_SCHNAK_ADJOINT)), key_bits(wsc));
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             if (wsc) wind_ops(0);       // level counter = n: wind.t = t_n (helpers.py:664,679)
             // q first (helpers.py:683-686): Mat_q = M + dt*(Dv*Ad - omega2*A' + gamma*M_u2(u_n))
@@ -501,7 +501,7 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
             fg.weighted_mass(wn_, ctx->d_trN, batch);
             int r = fg.launch();
             if (r != FEMFCT_OK) return r;
-            r = femfct_enqueue_species_solve(ctx, 13, ctx->d_trMat, 0, ctx->d_trRhs2, L(q_traj, 1), ts, L(q_traj, 0), ts, batch, kbudget, dt * Dv);
+            r = femfct_enqueue_species_solve(ctx, SWEEP_SCHNAK_ADJOINT, ctx->d_trMat, 0, ctx->d_trRhs2, L(q_traj, 1), ts, L(q_traj, 0), ts, batch, kbudget, dt * Dv);
             if (r != FEMFCT_OK) return r;
             // then p by FCT (helpers.py:690-697): N = gamma*M - 2*gamma*M_uv (above), rhs = -2*gamma*u_n*v_n*q_n
             LoadSpec lp;
@@ -516,8 +516,8 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
             return femfct_enqueue_step_end(ctx, -1, batch, true);
         });
     };
-    ctx->kind_fullrows.insert(13);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
-    return femfct_run_sweep(ctx, 13, num_steps, batch, num_steps - 1, true, begin, step);
+    // (diffusion / reaction terms: rows with both entries of a pair from the start: full rows)
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SCHNAK_ADJOINT, num_steps, batch, num_steps - 1, true, true}, begin, step);
 }
 
 // ------------------------------------------------------------------ chemotaxis
@@ -538,18 +538,18 @@ static int chtxs_forward(femfct_ctx* ctx, Ctl c, double* u_traj, double* v_traj,
         return femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trBase, 1);
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY(c.tag(14), key_bits(c.base), key_bits(u_traj), key_bits(v_traj), key_bits(num_steps),
+        auto key = KEY(c.tag(SWEEP_CHTXS_FORWARD), key_bits(c.base), key_bits(u_traj), key_bits(v_traj), key_bits(num_steps),
                        key_bits(dt), key_bits(delta), key_bits(Dm), key_bits(Df), key_bits(chi), key_bits(eta),
                        key_bits(rescaling), key_bits(batch), key_bits((int32_t)budget), key_bits((int32_t)kbudget),
                        key_bits(ctx->rel_tol), key_bits(ctx->kry_tol),
-                       key_bits((int32_t)femfct_species_cheb(ctx, 14)));
+                       key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_CHTXS_FORWARD)));
         c.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
             LoadSpec l2;  // assemble(v_n*v*dx + dt*c*u_n/r*v*dx)  (helpers.py:1339-1340)
             l2.s0 = 1.0; l2.mx = L(v_traj, 0); l2.mx_bs = ts; l2.s1 = dt / rescaling; l2.k2 = 1.0;
             l2.q1 = c.ref(L); l2.q1_bs = c.bs(n, ts); l2.q2 = L(u_traj, 0); l2.q2_bs = ts;
             femfct_enqueue_load(ctx, l2, ctx->d_trRhs2, batch);
-            int r = femfct_enqueue_species_solve(ctx, 14, ctx->d_trBase, 1, ctx->d_trRhs2, L(v_traj, 0), ts, L(v_traj, 1), ts, batch, kbudget, dt * Df);
+            int r = femfct_enqueue_species_solve(ctx, SWEEP_CHTXS_FORWARD, ctx->d_trBase, 1, ctx->d_trRhs2, L(v_traj, 0), ts, L(v_traj, 1), ts, batch, kbudget, dt * Df);
             if (r != FEMFCT_OK) return r;
             // A_var1 = Dm*Ad - chi*Aa(u_n, v_{n+1})  (helpers.py:1350-1352)
             femfct_enqueue_chtxs_matrix(ctx, 0, L(u_traj, 0), ts, L(v_traj, 1), ts, Dm, chi, eta, ctx->d_trA, batch);
@@ -560,8 +560,8 @@ static int chtxs_forward(femfct_ctx* ctx, Ctl c, double* u_traj, double* v_traj,
             return femfct_enqueue_step_end(ctx, 1, batch, true);
         });
     };
-    ctx->kind_fullrows.insert(14);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
-    return femfct_run_sweep(ctx, 14, num_steps, batch, 0, true, begin, step);
+    // (diffusion / reaction terms: rows with both entries of a pair from the start: full rows)
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_CHTXS_FORWARD, num_steps, batch, 0, true, true}, begin, step);
 }
 
 // c_level: the frozen control level (helpers.py:1332-1333), n doubles per batch member
@@ -604,11 +604,11 @@ int femfct_chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
         return FEMFCT_OK;
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY((uint64_t)15, key_bits(u_traj), key_bits(v_traj), key_bits(uhat), key_bits(vhat), key_bits(p_traj),
+        auto key = KEY((uint64_t)SWEEP_CHTXS_ADJOINT, key_bits(u_traj), key_bits(v_traj), key_bits(uhat), key_bits(vhat), key_bits(p_traj),
                        key_bits(q_traj), key_bits(c_traj), key_bits(num_steps), key_bits(dt), key_bits(delta),
                        key_bits(Dm), key_bits(Df), key_bits(chi), key_bits(eta), key_bits(rescaling), key_bits(alltime),
                        key_bits(batch), key_bits((int32_t)budget), key_bits((int32_t)kbudget), key_bits(ctx->rel_tol),
-                       key_bits(ctx->kry_tol), key_bits((int32_t)femfct_species_cheb(ctx, 15)));
+                       key_bits(ctx->kry_tol), key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_CHTXS_ADJOINT)));
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             // Mat_p = Dm*Ad - chi*Aa'(u_n, v_n)  (helpers.py:1499-1503)
             LoadSpec lp;  // assemble(c_n*q_{n+1}/r*w*dx) [+ uhat_n - u_n]  (helpers.py:1505-1507)
@@ -628,13 +628,13 @@ int femfct_chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
             femfct_enqueue_chtxs_rhs_q(ctx, L(u_traj, 0), ts, L(p_traj, 0), ts, chi, eta, alltime ? L(vhat, 0) : none, ts,
                                        alltime ? L(v_traj, 0) : none, ts, ctx->d_trRhs2, batch, L(q_traj, 1), ts, 1.0, dt);
             femfct_request_fused_end(ctx, -1, true);
-            r = femfct_enqueue_species_solve(ctx, 15, ctx->d_trBase, 1, ctx->d_trRhs2, L(q_traj, 1), ts, L(q_traj, 0), ts, batch, kbudget, dt * Df);
+            r = femfct_enqueue_species_solve(ctx, SWEEP_CHTXS_ADJOINT, ctx->d_trBase, 1, ctx->d_trRhs2, L(q_traj, 1), ts, L(q_traj, 0), ts, batch, kbudget, dt * Df);
             if (r != FEMFCT_OK) return r;
             return femfct_enqueue_step_end(ctx, -1, batch, true);
         });
     };
-    ctx->kind_fullrows.insert(15);      // (diffusion / reaction terms: rows with both entries of a pair from the start)
-    return femfct_run_sweep(ctx, 15, num_steps, batch, num_steps - 1, true, begin, step);
+    // (diffusion / reaction terms: rows with both entries of a pair from the start: full rows)
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_CHTXS_ADJOINT, num_steps, batch, num_steps - 1, true, true}, begin, step);
 }
 
 // BiCGStab diagnostics of the most recent sweep that used it: info_host[step*batch + b]
