@@ -222,6 +222,8 @@ struct femfct_ctx {
     double *d_trRhs2 = nullptr, *d_trTmp = nullptr;                        // [B*n]
     double* d_wscale = nullptr;     // per-level factors s(t_k) of a separable time-dependent wind [wscale_count]
     size_t wscale_count = 0;
+    double* d_zero_traj = nullptr;  // zero drift control of the linear sweeps with a reaction term [zero_traj_count]
+    size_t zero_traj_count = 0;
 
     // scratch for reductions (kernels_pgd.hip)
     double* d_scratch = nullptr;

@@ -31,6 +31,12 @@ struct LoadSpec {
     int64_t mx_bs = 0, p1_bs = 0, q1_bs = 0, q2_bs = 0, q3_bs = 0, da_bs = 0, db_bs = 0, ea_bs = 0, eb_bs = 0;
 };
 
+// out_i = (M (a - b))_i - sum_j (int g_h phi_i phi_j) x_j   (kernels_react.hip; a absent: no mass term, b absent: M a)
+struct ReactLoadSpec {
+    VecRef a{nullptr, nullptr, 0, 0}, b{nullptr, nullptr, 0, 0}, g{nullptr, nullptr, 0, 0}, x{nullptr, nullptr, 0, 0};
+    int64_t a_bs = 0, b_bs = 0, g_bs = 0, x_bs = 0;
+};
+
 // up to three independent forms of a time step in one launch (kernels_forms.hip: k_forms2 / k_forms3)
 enum { FORM_NONE = 0, FORM_WMASS, FORM_LOAD, FORM_CHTXS_MAT0, FORM_CHTXS_MAT1 };
 struct ChtxsMatSpec {
@@ -63,6 +69,7 @@ struct FormGroup {
 MeshArgs femfct_mesh_args(const femfct_ctx* ctx);
 int femfct_enqueue_weighted_mass(femfct_ctx* ctx, const WMassSpec& sp, double* out, int32_t batch);
 int femfct_enqueue_load(femfct_ctx* ctx, const LoadSpec& sp, double* out, int32_t batch);
+int femfct_enqueue_react_load(femfct_ctx* ctx, const ReactLoadSpec& sp, double* out, int32_t batch);
 int femfct_enqueue_chtxs_matrix(femfct_ctx* ctx, int adjoint, VecRef u, int64_t u_bs, VecRef v, int64_t v_bs,
                                 double Dm, double chi, double eta, double* out, int32_t batch);
 // mx.base != null: out = s0 * M mx + s2 * rhs_q in the same pass (the species right-hand side, helpers.py:1538)

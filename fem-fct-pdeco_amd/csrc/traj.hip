@@ -166,20 +166,13 @@ int femfct_ensure_traj_ws(femfct_ctx* ctx, int32_t batch, int32_t steps) {
     return FEMFCT_OK;
 }
 
-extern "C" {
-
-int femfct_solidbody_forward(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
-                             double* u_traj, int32_t num_steps, double dt, double eps, double rot_scale, double bx,
-                             double by, int32_t batch) {
-    return femfct_solidbody_forward_src(ctx, Arot_ell, c_traj, c_shared, nullptr, u_traj, num_steps, dt, eps, rot_scale, bx,
-                                        by, batch);
-}
-
 // the same sweep with a source trajectory: rhs_{n+1} = assemble(src_{n+1} * v * dx) = M src_{n+1}
 // (advection_FCT_PDECO_alltime_exact.py:249-253: u_rhs = assemble((g_np1 + c_np1)*v*dx), A_u = A - eps*Ad)
-int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
-                                 const double* src_traj, double* u_traj, int32_t num_steps, double dt, double eps,
-                                 double rot_scale, double bx, double by, int32_t batch) {
+// g_traj (may be null): coefficient trajectory of an explicit reaction term, shared by the batch:
+// rhs_{n+1} = M src_{n+1} - Mg(g_n) u_n in one launch (advection_FCT_PDECO_finaltime_exact.py:273-277)
+static int solidbody_forward_sweep(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                                   const double* src_traj, const double* g_traj, double* u_traj, int32_t num_steps,
+                                   double dt, double eps, double rot_scale, double bx, double by, int32_t batch) {
     FEMFCT_ENTER(ctx);
     ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
     ARG_TRY(ctx, c_traj && u_traj && num_steps >= 1 && dt > 0 && batch >= 1, "bad argument");
@@ -210,7 +203,7 @@ int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const 
                                  key_bits(num_steps), key_bits(dt), key_bits(eps), key_bits(rot_scale), key_bits(bx),
                                  key_bits(by), key_bits(batch), key_bits((int32_t)budget), key_bits(ctx->rel_tol),
                                  key_bits(pre ? Aall.base : nullptr), key_bits(src_traj), key_bits((int32_t)inl),
-                                 key_bits((int32_t)rotg), key_bits(rot_om)};
+                                 key_bits((int32_t)rotg), key_bits(rot_om), key_bits(g_traj)};
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
             // control at level n+1 (finaltime.py:185), state from level n into level n+1
             MatRef A = Aall;
@@ -223,7 +216,14 @@ int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const 
                 A = MatRef{ctx->d_trA, nullptr, 0, 0, (int64_t)ctx->W * n};
             }
             VecRef rhs = make_ref(nullptr);
-            if (src_traj) {
+            if (g_traj) {       // source at level n+1, coefficient and state at level n
+                ReactLoadSpec rl;
+                rl.a = lref(ctx, src_traj, lv, n, 1); rl.a_bs = tstride;
+                rl.g = lref(ctx, g_traj, lv, n, 0);   rl.g_bs = 0;
+                rl.x = lref(ctx, u_traj, lv, n, 0);   rl.x_bs = tstride;
+                femfct_enqueue_react_load(ctx, rl, ctx->d_trRhs, batch);
+                rhs = make_ref(ctx->d_trRhs);
+            } else if (src_traj) {
                 femfct_enqueue_mass_diff(ctx, lref(ctx, src_traj, lv, n, 1), tstride, make_ref(nullptr), 0, ctx->d_trRhs, batch);
                 rhs = make_ref(ctx->d_trRhs);
             }
@@ -236,13 +236,17 @@ int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const 
             return FEMFCT_OK;
         });
     };
-    // (a diffusive operator has no upwind rows: no point in finding that out from a whole sweep with the pair-compact launch)
-    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SOLIDBODY_FORWARD, num_steps, batch, 0, false, eps != 0.0}, begin, step);
+    // (a diffusive operator has no upwind rows: no point in finding that out from a whole sweep with the pair-compact launch;
+    // nor has the operator of a sweep with a reaction term, whose adjoint carries a mass-like part)
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SOLIDBODY_FORWARD, num_steps, batch, 0, false, g_traj || eps != 0.0}, begin, step);
 }
 
-int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
-                             const double* u_traj, const double* uhat, double* p_traj, int32_t num_steps, double dt,
-                             double eps, double rot_scale, double bx, double by, int32_t alltime, int32_t batch) {
+// g_traj (may be null): rhs_n = [M (uhat_n - u_n)] - Mg(g_n) p_{n+1}, the coefficient at the level being produced
+// (advection_FCT_PDECO_finaltime_exact.py:317-321); the final-time sweep has a right-hand side then, too
+static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                                   const double* g_traj, const double* u_traj, const double* uhat, double* p_traj,
+                                   int32_t num_steps, double dt, double eps, double rot_scale, double bx, double by,
+                                   int32_t alltime, int32_t batch) {
     FEMFCT_ENTER(ctx);
     ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
     ARG_TRY(ctx, c_traj && u_traj && uhat && p_traj && num_steps >= 1 && dt > 0 && batch >= 1, "bad argument");
@@ -278,7 +282,7 @@ int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const doub
                                  key_bits(uhat), key_bits(p_traj), key_bits(num_steps), key_bits(dt), key_bits(eps),
                                  key_bits(rot_scale), key_bits(bx), key_bits(by), key_bits(alltime), key_bits(batch),
                                  key_bits((int32_t)budget), key_bits(ctx->rel_tol), key_bits(pre ? Aall.base : nullptr),
-                                 key_bits((int32_t)inl), key_bits((int32_t)rotg), key_bits(rot_om)};
+                                 key_bits((int32_t)inl), key_bits((int32_t)rotg), key_bits(rot_om), key_bits(g_traj)};
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             // level counter = n: control c_n (finaltime.py:213), p_{n+1} -> p_n
             MatRef A = Aall;
@@ -291,7 +295,17 @@ int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const doub
                 A = MatRef{ctx->d_trA, nullptr, 0, 0, (int64_t)ctx->W * n};
             }
             VecRef rhs = make_ref(nullptr);
-            if (alltime) {  // rhs = assemble((uhat_n - u_n) v dx)  (alltime.py:257)
+            if (g_traj) {   // coefficient at level n, adjoint at level n+1; all-time: the misfit load in the same launch
+                ReactLoadSpec rl;
+                if (alltime) {
+                    rl.a = lref(ctx, uhat, lv, n, 0);   rl.a_bs = tstride;
+                    rl.b = lref(ctx, u_traj, lv, n, 0); rl.b_bs = tstride;
+                }
+                rl.g = lref(ctx, g_traj, lv, n, 0); rl.g_bs = 0;
+                rl.x = lref(ctx, p_traj, lv, n, 1); rl.x_bs = tstride;
+                femfct_enqueue_react_load(ctx, rl, ctx->d_trRhs, batch);
+                rhs = make_ref(ctx->d_trRhs);
+            } else if (alltime) {  // rhs = assemble((uhat_n - u_n) v dx)  (alltime.py:257)
                 femfct_enqueue_mass_diff(ctx, lref(ctx, uhat, lv, n, 0), tstride, lref(ctx, u_traj, lv, n, 0), tstride,
                                          ctx->d_trRhs, batch);
                 rhs = make_ref(ctx->d_trRhs);
@@ -304,7 +318,72 @@ int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const doub
             return FEMFCT_OK;
         });
     };
-    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SOLIDBODY_ADJOINT, num_steps, batch, num_steps - 1, false, eps != 0.0}, begin, step);
+    return femfct_run_sweep(ctx, SweepSpec{SWEEP_SOLIDBODY_ADJOINT, num_steps, batch, num_steps - 1, false, g_traj || eps != 0.0}, begin, step);
+}
+
+// the zero drift control of the linear sweeps (the control enters through the source): (num_steps + 1) * n zeros
+static int zero_control(femfct_ctx* ctx, int32_t num_steps, const double** out) {
+    const size_t count = (size_t)(num_steps + 1) * ctx->n;
+    if (count > ctx->zero_traj_count) {
+        femfct_drop_graphs(ctx);
+        if (ctx->d_zero_traj) hipFree(ctx->d_zero_traj);
+        ctx->d_zero_traj = nullptr; ctx->zero_traj_count = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_zero_traj, sizeof(double) * count));
+        ctx->zero_traj_count = count;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_zero_traj, 0, sizeof(double) * count, ctx->stream));
+    }
+    *out = ctx->d_zero_traj;
+    return FEMFCT_OK;
+}
+
+extern "C" {
+
+int femfct_solidbody_forward(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                             double* u_traj, int32_t num_steps, double dt, double eps, double rot_scale, double bx,
+                             double by, int32_t batch) {
+    return femfct_solidbody_forward_src(ctx, Arot_ell, c_traj, c_shared, nullptr, u_traj, num_steps, dt, eps, rot_scale, bx,
+                                        by, batch);
+}
+
+int femfct_solidbody_forward_src(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                                 const double* src_traj, double* u_traj, int32_t num_steps, double dt, double eps,
+                                 double rot_scale, double bx, double by, int32_t batch) {
+    return solidbody_forward_sweep(ctx, Arot_ell, c_traj, c_shared, src_traj, nullptr, u_traj, num_steps, dt, eps, rot_scale,
+                                   bx, by, batch);
+}
+
+int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                             const double* u_traj, const double* uhat, double* p_traj, int32_t num_steps, double dt,
+                             double eps, double rot_scale, double bx, double by, int32_t alltime, int32_t batch) {
+    return solidbody_adjoint_sweep(ctx, Arot_ell, c_traj, c_shared, nullptr, u_traj, uhat, p_traj, num_steps, dt, eps,
+                                   rot_scale, bx, by, alltime, batch);
+}
+
+// Linear advection-diffusion-reaction, du/dt - eps lap u + div(w u) + g u = src, the reaction term explicit:
+// advection_FCT_PDECO_finaltime_exact.py:252-279 (state), :344-370 (sensitivity: src = d, zero initial condition)
+int femfct_linear_forward_react(femfct_ctx* ctx, const double* A_ell, const double* src_traj, const double* g_traj,
+                                double* u_traj, int32_t num_steps, double dt, double eps, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
+    ARG_TRY(ctx, A_ell && g_traj && u_traj && num_steps >= 1 && batch >= 1, "bad argument");
+    const double* zc = nullptr;
+    int rc = zero_control(ctx, num_steps, &zc);
+    if (rc != FEMFCT_OK) return rc;
+    return solidbody_forward_sweep(ctx, A_ell, zc, 1, src_traj, g_traj, u_traj, num_steps, dt, eps, 1.0, 0.0, 0.0, batch);
+}
+
+// its adjoint, :293-322: A_p = -Aadj - eps*Ad with Aadj = Aa1 + Aa2 given
+int femfct_linear_adjoint_react(femfct_ctx* ctx, const double* Aadj_ell, const double* g_traj, const double* u_traj,
+                                const double* uhat, double* p_traj, int32_t num_steps, double dt, double eps,
+                                int32_t alltime, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
+    ARG_TRY(ctx, Aadj_ell && g_traj && u_traj && uhat && p_traj && num_steps >= 1 && batch >= 1, "bad argument");
+    const double* zc = nullptr;
+    int rc = zero_control(ctx, num_steps, &zc);
+    if (rc != FEMFCT_OK) return rc;
+    return solidbody_adjoint_sweep(ctx, Aadj_ell, zc, 1, g_traj, u_traj, uhat, p_traj, num_steps, dt, eps, 1.0, 0.0, 0.0,
+                                   alltime, batch);
 }
 
 // per-step solver diagnostics of the most recent trajectory sweep: info[step*batch + b]

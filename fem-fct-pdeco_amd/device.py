@@ -331,6 +331,30 @@ class Context:
             int(num_steps), float(dt), float(eps), float(rot_scale), float(drift[0]), float(drift[1]),
             int(bool(alltime)), int(batch)))
 
+    def linear_forward_react(self, A, src_traj, g_traj, u_traj, num_steps, dt, eps, batch=1):
+        """State / sensitivity sweep with the explicit reaction term: rhs_{n+1} = M src_{n+1} - Mg(g_n) u_n
+        (``src_traj`` may be None); ``g_traj`` is one coefficient trajectory for the whole batch."""
+        check(self.handle, lib.femfct_linear_forward_react(self.handle, dptr(A), dptr(src_traj), dptr(g_traj), dptr(u_traj),
+                                                           int(num_steps), float(dt), float(eps), int(batch)))
+
+    def linear_adjoint_react(self, Aadj, g_traj, u_traj, uhat, p_traj, num_steps, dt, eps, alltime=False, batch=1):
+        """Adjoint sweep with the explicit reaction term: rhs_n = -Mg(g_n) p_{n+1} (+ M (uhat_n - u_n) all-time) and the
+        operator -Aadj - eps*Ad, ``Aadj = Aa1 + Aa2``."""
+        check(self.handle, lib.femfct_linear_adjoint_react(self.handle, dptr(Aadj), dptr(g_traj), dptr(u_traj), dptr(uhat),
+                                                           dptr(p_traj), int(num_steps), float(dt), float(eps),
+                                                           int(bool(alltime)), int(batch)))
+
+    def react_load(self, src, g, x, out, batch=1):
+        """out = M src - Mg(g) x for one level, matrix-free (``src`` may be None); ``g`` is shared by the batch."""
+        check(self.handle, lib.femfct_react_load(self.handle, dptr(src), dptr(g), dptr(x), dptr(out), int(batch)))
+
+    def assemble_weighted_mass(self, f, out: DeviceArray | None = None) -> DeviceArray:
+        """``assemble_sparse(f_h*u*v*dx)`` for the P1 function with the nodal values ``f`` (ELL)."""
+        if out is None:
+            out = self.empty(self.W * self.n)
+        check(self.handle, lib.femfct_assemble_weighted_mass(self.handle, dptr(f), dptr(out)))
+        return out
+
     def traj_info(self, num_steps, batch=1):
         arr = (StepInfo * (num_steps * batch))()
         check(self.handle, lib.femfct_traj_info(self.handle, arr, int(num_steps), int(batch)))

@@ -13,6 +13,7 @@ Mirrors the time loops the reference writes in Python around ``FCT_alg[_ref]``
   linear advection-diffusion + distributed source control (pgd_source_control)
       loop      advection_FCT_PDECO_alltime_exact.py:212-330, advection_FCT_PDECO_finaltime.py:170-280
       errors    advection_FCT_PDECO_alltime_exact.py:333-440
+      reaction  advection_FCT_PDECO_finaltime_exact.py (LinearReactionSourceControl, finaltime_exact_fields)
 
 NumPy-facing methods take/return ``(num_steps+1)*nodes`` float64 arrays in FEniCS
 DoF order, mutate the state array in place *and* return it, like the reference.
@@ -178,6 +179,88 @@ class LinearSourceControl(SolidBodyDrift):
             for a in (u, uh, p):
                 a.free()
         return pk
+
+
+class LinearReactionSourceControl(LinearSourceControl):
+    """The same problem family with a reaction term, du/dt - eps*lap(u) + div(w u) + g u = c + f, the final-time
+    manufactured-solution study advection_FCT_PDECO_finaltime_exact.py.  The reaction term is explicit (IMEX), as the
+    script runs it:
+
+        state / sensitivity (:252-279, :344-370)   rhs_i = M src_i - Mg(g_{i-1}) u_{i-1},  A_u = Aa1 - eps*Ad
+        adjoint (:293-322)                         rhs_i = -Mg(g_i) p_{i+1} [+ M (uhat_i - u_i) all-time],
+                                                   A_p = -(Aa1 + Aa2) - eps*Ad
+
+    with Mg(g) = assemble(g_h*u*v*dx) applied matrix-free in the step's load kernel.  ``react``: the coefficient
+    trajectory, (num_steps + 1) * nodes nodal values in the problem's DoF order, shared by every batch member.
+    ``adjoint_mass``: nodal values of a P1 field sigma ~ div(w), Aa2 = assemble(sigma_h*u*v*dx) (None: Aa2 = 0).  The
+    script builds Aa2 from a cellwise-constant L2 projection of div(w) instead; INTEGRATION.md states the difference.
+    ``solve_state`` / ``solve_adjoint_state`` are the parent's and run the sweeps below."""
+
+    def __init__(self, mesh, num_steps, dt, wind, react, eps=1e-4, adjoint_mass=None, batch=1, device_id=0,
+                 order=_lib.ORDER_FENICS):
+        react = np.asarray(react, dtype=np.float64).ravel()
+        tlen = (int(num_steps) + 1) * mesh.nodes
+        if react.size != tlen:
+            raise ValueError(f"react of {react.size} values, expected (num_steps + 1) * nodes = {tlen}")
+        if adjoint_mass is not None:
+            adjoint_mass = np.asarray(adjoint_mass, dtype=np.float64).ravel()
+            if adjoint_mass.size != mesh.nodes:
+                raise ValueError(f"adjoint_mass of {adjoint_mass.size} values, expected {mesh.nodes}")
+        super().__init__(mesh, num_steps, dt, wind, eps=eps, batch=batch, device_id=device_id, order=order)
+        self._react = self.ctx.array(react)
+        if adjoint_mass is None:
+            self.Aadj = self.Arot
+        else:
+            sig = self.ctx.array(adjoint_mass)
+            Aa2 = self.ctx.assemble_weighted_mass(sig)
+            self.Aadj = self.ctx.empty(self.ctx.W * self.n)
+            self.ctx.axpby(self.ctx.W * self.n, 1.0, self.Arot, 1.0, Aa2, self.Aadj)
+            sig.free()
+            Aa2.free()
+
+    def state(self, src: DeviceArray, u: DeviceArray, batch=None):
+        self.ctx.linear_forward_react(self.Arot, src, self._react, u, self.num_steps, self.dt, self.eps,
+                                      self.batch if batch is None else batch)
+
+    def adjoint_state(self, u, uhat, p, optim="finaltime", batch=None):
+        if optim not in ("alltime", "finaltime"):
+            raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+        self.ctx.linear_adjoint_react(self.Aadj, self._react, u, uhat, p, self.num_steps, self.dt, self.eps,
+                                      optim == "alltime", self.batch if batch is None else batch)
+
+    def sensitivity(self, d, w):
+        _lib.check(self.ctx.handle, _lib.lib.femfct_memset0(self.ctx.handle, dptr(w), 8 * self.n))
+        self.state(d, w, batch=1)
+
+
+def finaltime_exact_wind(gamma=0.1, k3=1, k4=1):
+    """The wind of the final-time manufactured study on the unit square, w = gamma/2 * (sin 2 k3 pi x, sin 2 k4 pi y)
+    (advection_FCT_PDECO_finaltime_exact.py:140-151), as a ``wind(x, y) -> (wx, wy)`` callable."""
+    return lambda x, y: (gamma * np.sin(k3 * np.pi * x) * np.cos(k3 * np.pi * x),
+                         gamma * np.sin(k4 * np.pi * y) * np.cos(k4 * np.pi * y))
+
+
+def finaltime_exact_fields(t, X, Y, T=0.1, beta=0.1, c_lower=0.0, c_upper=1.0, e1=1.0, e2=1.0, k1=1, k2=1, k3=1, k4=1,
+                           eps=1e-4, gamma=0.1, delta_ex=0.1):
+    """Inputs of the manufactured problem of advection_FCT_PDECO_finaltime_exact.py:76-138 at time t on the grid X, Y
+    (unit square), with the script's defaults: state u = e^{e1 t} (cos k1 pi x cos k2 pi y + 1), adjoint
+    p = (e^{e2 T} - e^{e2 t}) cos k3 pi x cos k4 pi y, control c = clip(p / beta), reaction coefficient g, source f and
+    target uhat = u.  "div" is the analytic divergence of the wind, gamma pi (k3 cos 2 k3 pi x + k4 cos 2 k4 pi y)."""
+    pi = np.pi
+    et = np.exp(e1 * t)
+    cx1, sx1, cy2, sy2 = np.cos(k1 * pi * X), np.sin(k1 * pi * X), np.cos(k2 * pi * Y), np.sin(k2 * pi * Y)
+    u = et * (cx1 * cy2 + 1)
+    p = (np.exp(e2 * T) - np.exp(e2 * t)) * np.cos(k3 * pi * X) * np.cos(k4 * pi * Y)
+    c = np.clip(1 / beta * p, c_lower, c_upper)
+    g = (-e2 * np.exp(e2 * t) / (np.exp(e2 * T) - np.exp(e2 * t * (1 - delta_ex))) - eps * (k3 ** 2 + k4 ** 2) * pi ** 2
+         - gamma * pi * (k3 * np.sin(k3 * pi * X) ** 2 + k4 * np.sin(k4 * pi * Y) ** 2))
+    wx, wy = finaltime_exact_wind(gamma, k3, k4)(X, Y)
+    div = gamma * pi * (k3 * np.cos(2 * k3 * pi * X) + k4 * np.cos(2 * k4 * pi * Y))
+    f = (e1 * u                                                     # du/dt
+         + eps * (k1 ** 2 + k2 ** 2) * pi ** 2 * (u - et)           # -eps lap u
+         + div * u - et * pi * (k1 * wx * sx1 * cy2 + k2 * wy * cx1 * sy2)      # div(w u) = div(w) u + w . grad u
+         + g * u - c)
+    return dict(u=u, p=p, c=c, g=g, f=f, uhat=u.copy(), div=div)
 
 
 def pgd_solidbody_finaltime(prob: SolidBodyDrift, u0, uhat_T, c0, beta, c_lower, c_upper, iters,

@@ -243,6 +243,26 @@ int femfct_solidbody_adjoint(femfct_ctx* ctx, const double* Arot_ell, const doub
                              const double* u_traj, const double* uhat, double* p_traj, int32_t num_steps,
                              double dt, double eps, double rot_scale, double bx, double by, int32_t alltime,
                              int32_t batch);
+/* Linear advection-diffusion-reaction with an explicit (IMEX) reaction term, du/dt - eps*lap(u) + div(w u) + g u = src
+ * (advection_FCT_PDECO_finaltime_exact.py; added after ABI version 5, backward compatible).  g_traj: nodal values of the
+ * P1 coefficient at every level, one trajectory shared by the batch.
+ * State / sensitivity sweep, :252-279 and :344-370: rhs_{n+1} = assemble(src_{n+1}*v*dx) - Mg(g_n) u_n with
+ * Mg(g) = assemble(g_h*u*v*dx), then FCT_alg(A - eps*Ad, ...); A_ell = assemble(dot(w, grad(v))*u*dx).  src_traj NULL: no
+ * source.  u level 0 = initial condition (in place). */
+int femfct_linear_forward_react(femfct_ctx* ctx, const double* A_ell, const double* src_traj, const double* g_traj,
+                                double* u_traj, int32_t num_steps, double dt, double eps, int32_t batch);
+/* Adjoint sweep, :293-322: rhs_n = -Mg(g_n) p_{n+1} (alltime != 0: + assemble((uhat_n - u_n)*v*dx)), then
+ * FCT_alg(-Aadj - eps*Ad, ...) with Aadj_ell = Aa1 + Aa2, Aa2 = assemble(sigma_h*u*v*dx) for a nodal sigma ~ div(w).
+ * Terminal condition and uhat as in femfct_solidbody_adjoint. */
+int femfct_linear_adjoint_react(femfct_ctx* ctx, const double* Aadj_ell, const double* g_traj, const double* u_traj,
+                                const double* uhat, double* p_traj, int32_t num_steps, double dt, double eps,
+                                int32_t alltime, int32_t batch);
+/* the load of one level on its own: out = M src - Mg(g) x, matrix-free; g is n doubles shared by the batch, src (may be
+ * NULL: no M src term), x and out are n doubles per batch member */
+int femfct_react_load(femfct_ctx* ctx, const double* src_dev, const double* g_dev, const double* x_dev, double* out_dev,
+                      int32_t batch);
+/* out_ell = assemble(f_h*u*v*dx) for the P1 function with nodal values f_dev (n doubles).  Synchronises. */
+int femfct_assemble_weighted_mass(femfct_ctx* ctx, const double* f_dev, double* out_ell);
 /* solver diagnostics of the most recent sweep: info_host[step*batch + b] */
 int femfct_traj_info(femfct_ctx* ctx, femfct_step_info* info_host, int32_t num_steps, int32_t batch);
 
