@@ -135,6 +135,8 @@ SIGNATURES = {
     "femfct_nonlinear_forward_ct": (C.c_int, [_p, _p, _p, _i, _p, _i, _d, _d, _i]),
     "femfct_schnak_forward_ct": (C.c_int, [_p, _p, _p, _p, _i, _p, _p, _i, _d, _p, _d, _i]),
     "femfct_chtxs_forward_ct": (C.c_int, [_p, _p, _i, _p, _p, _i, _d, _p, _d, _i]),
+    "femfct_chtxs_forward_g": (C.c_int, [_p, _p, _i, _i, _p, _p, _i, _d, _p, _d, _p, _i]),
+    "femfct_chtxs_adjoint_g": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _p, _d, _i, _p, _i]),
     "femfct_nonlinear_adjoint_alltime": (C.c_int, [_p, _p, _p, _p, _i, _p, _i, _d, _d, _i]),
     "femfct_chtxs_adjoint": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _p, _d, _i, _i]),
     "femfct_traj_krylov_info": (C.c_int, [_p, C.POINTER(StepInfo), _i, _i]),

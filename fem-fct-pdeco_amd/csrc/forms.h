@@ -37,6 +37,16 @@ struct ReactLoadSpec {
     int64_t a_bs = 0, b_bs = 0, g_bs = 0, x_bs = 0;
 };
 
+// out_i = s1 * int q1 q2 phi_i + s2*(da_i - db_i) + int (g0 + g1*a + g2*a^2) a^e b phi_i   (kernels_growth.hip: the growth
+// term of the chemotaxis system; b absent: 1, q1 / da absent: no such term)
+struct GrowthLoadSpec {
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0, s1 = 0.0, s2 = 0.0;
+    int e = 0;
+    VecRef a{nullptr, nullptr, 0, 0}, b{nullptr, nullptr, 0, 0}, q1{nullptr, nullptr, 0, 0}, q2{nullptr, nullptr, 0, 0},
+        da{nullptr, nullptr, 0, 0}, db{nullptr, nullptr, 0, 0};
+    int64_t a_bs = 0, b_bs = 0, q1_bs = 0, q2_bs = 0, da_bs = 0, db_bs = 0;
+};
+
 // up to three independent forms of a time step in one launch (kernels_forms.hip: k_forms2 / k_forms3)
 enum { FORM_NONE = 0, FORM_WMASS, FORM_LOAD, FORM_CHTXS_MAT0, FORM_CHTXS_MAT1 };
 struct ChtxsMatSpec {
@@ -72,6 +82,10 @@ int femfct_enqueue_load(femfct_ctx* ctx, const LoadSpec& sp, double* out, int32_
 int femfct_enqueue_react_load(femfct_ctx* ctx, const ReactLoadSpec& sp, double* out, int32_t batch);
 int femfct_enqueue_chtxs_matrix(femfct_ctx* ctx, int adjoint, VecRef u, int64_t u_bs, VecRef v, int64_t v_bs,
                                 double Dm, double chi, double eta, double* out, int32_t batch);
+int femfct_enqueue_growth_load(femfct_ctx* ctx, const GrowthLoadSpec& sp, double* out, int32_t batch);
+// the chemotaxis flux matrix of a step (c.p0, p1, p2 = Dm, chi, eta) and its growth load in one launch
+int femfct_enqueue_chtxs_matrix_growth(femfct_ctx* ctx, int adjoint, const ChtxsMatSpec& c, double* mat_out,
+                                       const GrowthLoadSpec& sp, double* load_out, int32_t batch);
 // mx.base != null: out = s0 * M mx + s2 * rhs_q in the same pass (the species right-hand side, helpers.py:1538)
 int femfct_enqueue_chtxs_rhs_q(femfct_ctx* ctx, VecRef u, int64_t u_bs, VecRef p, int64_t p_bs, double chi, double eta,
                                VecRef da, int64_t da_bs, VecRef db, int64_t db_bs, double* out, int32_t batch,

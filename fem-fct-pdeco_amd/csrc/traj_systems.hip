@@ -6,6 +6,8 @@
 // species] -> [log + advance level]; captured once as a hipGraph and replayed per step.
 #include "traj_common.h"
 
+#include <cmath>
+
 
 namespace {
 
@@ -87,6 +89,28 @@ struct Ctl {
     uint64_t tag(int kind) const { return (uint64_t)(per_step ? kind + 100 : kind); }
     void key_tail(femfct_ctx::GraphKey& k) const { if (per_step) { k.push_back(key_bits((int32_t)1)); k.push_back(key_bits(shared)); } }
 };
+
+// Growth term r(u) = u (r0 + r1 u + r2 u^2) of the chemotaxis cell equation (kernels_growth.hip).  Absent (a null pointer, or
+// r = 0): the sweeps enqueue what they enqueue without it.  Graph keys: a sweep with growth carries its own tag
+// (kind + 200) and the three coefficients; the sweep kind (budgets, full rows) is the chemotaxis one, the operator being the same.
+struct Growth {
+    bool on = false;
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+    uint64_t tag(uint64_t t) const { return on ? t + 200 : t; }
+    void key_tail(femfct_ctx::GraphKey& k) const {
+        if (on) { k.push_back(key_bits(r0)); k.push_back(key_bits(r1)); k.push_back(key_bits(r2)); }
+    }
+};
+
+int parse_growth(femfct_ctx* ctx, const double* growth, Growth* g) {
+    *g = Growth{};
+    if (!growth) return FEMFCT_OK;
+    ARG_TRY(ctx, std::isfinite(growth[0]) && std::isfinite(growth[1]) && std::isfinite(growth[2]),
+            "growth coefficients must be finite");
+    g->r0 = growth[0]; g->r1 = growth[1]; g->r2 = growth[2];
+    g->on = g->r0 != 0.0 || g->r1 != 0.0 || g->r2 != 0.0;
+    return FEMFCT_OK;
+}
 
 int check_common(femfct_ctx* ctx, int32_t num_steps, double dt, int32_t batch) {
     ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
@@ -521,11 +545,15 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
 }
 
 // ------------------------------------------------------------------ chemotaxis
-// helpers.py:1250-1385.  par = {delta, Dm, Df, chi, eta}; the control: see Ctl
+// helpers.py:1250-1385.  par = {delta, Dm, Df, chi, eta}; the control: see Ctl; growth: see Growth (null: none).  With
+// growth the FCT step of the cell equation gets rhs = assemble(r(u_n)*v*dx) in place of zeros (helpers.py:1353;
+// mimura_data_helpers.py:65-70), evaluated in the launch that builds the chemotaxis matrix.
 static int chtxs_forward(femfct_ctx* ctx, Ctl c, double* u_traj, double* v_traj, int32_t num_steps, double dt,
-                         const double* par, double rescaling, int32_t batch) {
+                         const double* par, double rescaling, const double* growth, int32_t batch) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
+    Growth gw;
+    if ((rc = parse_growth(ctx, growth, &gw)) != FEMFCT_OK) return rc;
     ARG_TRY(ctx, c.base && u_traj && v_traj && par && rescaling != 0.0, "bad argument");
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_krylov_ws(ctx, batch)) != FEMFCT_OK) return rc;
@@ -538,12 +566,13 @@ static int chtxs_forward(femfct_ctx* ctx, Ctl c, double* u_traj, double* v_traj,
         return femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trBase, 1);
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY(c.tag(SWEEP_CHTXS_FORWARD), key_bits(c.base), key_bits(u_traj), key_bits(v_traj), key_bits(num_steps),
+        auto key = KEY(gw.tag(c.tag(SWEEP_CHTXS_FORWARD)), key_bits(c.base), key_bits(u_traj), key_bits(v_traj), key_bits(num_steps),
                        key_bits(dt), key_bits(delta), key_bits(Dm), key_bits(Df), key_bits(chi), key_bits(eta),
                        key_bits(rescaling), key_bits(batch), key_bits((int32_t)budget), key_bits((int32_t)kbudget),
                        key_bits(ctx->rel_tol), key_bits(ctx->kry_tol),
                        key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_CHTXS_FORWARD)));
         c.key_tail(key);
+        gw.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, +1, [&]() {
             LoadSpec l2;  // assemble(v_n*v*dx + dt*c*u_n/r*v*dx)  (helpers.py:1339-1340)
             l2.s0 = 1.0; l2.mx = L(v_traj, 0); l2.mx_bs = ts; l2.s1 = dt / rescaling; l2.k2 = 1.0;
@@ -552,9 +581,20 @@ static int chtxs_forward(femfct_ctx* ctx, Ctl c, double* u_traj, double* v_traj,
             int r = femfct_enqueue_species_solve(ctx, SWEEP_CHTXS_FORWARD, ctx->d_trBase, 1, ctx->d_trRhs2, L(v_traj, 0), ts, L(v_traj, 1), ts, batch, kbudget, dt * Df);
             if (r != FEMFCT_OK) return r;
             // A_var1 = Dm*Ad - chi*Aa(u_n, v_{n+1})  (helpers.py:1350-1352)
-            femfct_enqueue_chtxs_matrix(ctx, 0, L(u_traj, 0), ts, L(v_traj, 1), ts, Dm, chi, eta, ctx->d_trA, batch);
+            VecRef rhs = make_ref(nullptr);
+            if (gw.on) {            // ... and assemble(r(u_n)*v*dx) in the same launch
+                ChtxsMatSpec cm;
+                cm.u = L(u_traj, 0); cm.u_bs = ts; cm.v = L(v_traj, 1); cm.v_bs = ts; cm.p0 = Dm; cm.p1 = chi; cm.p2 = eta;
+                GrowthLoadSpec gl;
+                gl.g0 = gw.r0; gl.g1 = gw.r1; gl.g2 = gw.r2; gl.e = 1; gl.a = L(u_traj, 0); gl.a_bs = ts;
+                r = femfct_enqueue_chtxs_matrix_growth(ctx, 0, cm, ctx->d_trA, gl, ctx->d_trRhs, batch);
+                if (r != FEMFCT_OK) return r;
+                rhs = make_ref(ctx->d_trRhs);
+            } else {
+                femfct_enqueue_chtxs_matrix(ctx, 0, L(u_traj, 0), ts, L(v_traj, 1), ts, Dm, chi, eta, ctx->d_trA, batch);
+            }
             femfct_request_fused_end(ctx, 1, true);
-            r = femfct_enqueue_step_ref(ctx, ctx->d_trA, nullptr, 0, make_ref(nullptr), 0, L(u_traj, 0), ts, dt,
+            r = femfct_enqueue_step_ref(ctx, ctx->d_trA, nullptr, 0, rhs, gw.on ? n : 0, L(u_traj, 0), ts, dt,
                                         L(u_traj, 1), ts, batch, budget);
             if (r != FEMFCT_OK) return r;
             return femfct_enqueue_step_end(ctx, 1, batch, true);
@@ -568,25 +608,39 @@ static int chtxs_forward(femfct_ctx* ctx, Ctl c, double* u_traj, double* v_traj,
 int femfct_chtxs_forward(femfct_ctx* ctx, const double* c_level, double* u_traj, double* v_traj, int32_t num_steps,
                          double dt, const double* par, double rescaling, int32_t batch) {
     FEMFCT_ENTER(ctx);
-    return chtxs_forward(ctx, Ctl::frozen(c_level), u_traj, v_traj, num_steps, dt, par, rescaling, batch);
+    return chtxs_forward(ctx, Ctl::frozen(c_level), u_traj, v_traj, num_steps, dt, par, rescaling, nullptr, batch);
 }
 
 // per-step control (chemotaxis_mimura_FCT_PGD_alltime.py:180-183: f_rhs = f_n + dt*c_{n+1}*m_n)
 int femfct_chtxs_forward_ct(femfct_ctx* ctx, const double* c_traj, int32_t c_shared, double* u_traj, double* v_traj,
                             int32_t num_steps, double dt, const double* par, double rescaling, int32_t batch) {
     FEMFCT_ENTER(ctx);
-    return chtxs_forward(ctx, Ctl::traj(c_traj, c_shared), u_traj, v_traj, num_steps, dt, par, rescaling, batch);
+    return chtxs_forward(ctx, Ctl::traj(c_traj, c_shared), u_traj, v_traj, num_steps, dt, par, rescaling, nullptr, batch);
+}
+
+// either control (c_per_step = 0: c is the frozen level, c_shared ignored) with the growth term r(u) = u (r0 + r1 u + r2 u^2),
+// growth = {r0, r1, r2}; NULL: no growth
+int femfct_chtxs_forward_g(femfct_ctx* ctx, const double* c, int32_t c_per_step, int32_t c_shared, double* u_traj,
+                           double* v_traj, int32_t num_steps, double dt, const double* par, double rescaling,
+                           const double* growth, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return chtxs_forward(ctx, c_per_step ? Ctl::traj(c, c_shared) : Ctl::frozen(c), u_traj, v_traj, num_steps, dt, par,
+                         rescaling, growth, batch);
 }
 
 // helpers.py:1387-1581.  alltime = 0: optim == "finaltime" (uhat/vhat: n doubles per member, terminal
 // conditions set); alltime = 1: optim == "alltime" (uhat/vhat trajectories, level num_steps of p/q left
 // as passed, raw nodal misfits added to the load vectors: helpers.py:1506-1507,1533-1534).
-int femfct_chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat,
+// growth (see Growth; null: none): the p equation gains -r'(u) p, treated explicitly like the c q_{n+1} term next to it:
+// rhs_p += assemble(r'(u_n)*p_{n+1}*w*dx), r'(u) = r0 + 2 r1 u + 3 r2 u^2, in the launch of the matrix and the load.
+static int chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat,
                          const double* vhat, double* p_traj, double* q_traj, const double* c_traj, int32_t num_steps,
-                         double dt, const double* par, double rescaling, int32_t alltime, int32_t batch) {
-    FEMFCT_ENTER(ctx);
+                         double dt, const double* par, double rescaling, int32_t alltime, const double* growth,
+                         int32_t batch) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
+    Growth gw;
+    if ((rc = parse_growth(ctx, growth, &gw)) != FEMFCT_OK) return rc;
     ARG_TRY(ctx, u_traj && v_traj && uhat && vhat && p_traj && q_traj && c_traj && par && rescaling != 0.0, "bad argument");
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_krylov_ws(ctx, batch)) != FEMFCT_OK) return rc;
@@ -604,20 +658,33 @@ int femfct_chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
         return FEMFCT_OK;
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY((uint64_t)SWEEP_CHTXS_ADJOINT, key_bits(u_traj), key_bits(v_traj), key_bits(uhat), key_bits(vhat), key_bits(p_traj),
+        auto key = KEY(gw.tag((uint64_t)SWEEP_CHTXS_ADJOINT), key_bits(u_traj), key_bits(v_traj), key_bits(uhat), key_bits(vhat), key_bits(p_traj),
                        key_bits(q_traj), key_bits(c_traj), key_bits(num_steps), key_bits(dt), key_bits(delta),
                        key_bits(Dm), key_bits(Df), key_bits(chi), key_bits(eta), key_bits(rescaling), key_bits(alltime),
                        key_bits(batch), key_bits((int32_t)budget), key_bits((int32_t)kbudget), key_bits(ctx->rel_tol),
                        key_bits(ctx->kry_tol), key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_CHTXS_ADJOINT)));
+        gw.key_tail(key);
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             // Mat_p = Dm*Ad - chi*Aa'(u_n, v_n)  (helpers.py:1499-1503)
             LoadSpec lp;  // assemble(c_n*q_{n+1}/r*w*dx) [+ uhat_n - u_n]  (helpers.py:1505-1507)
             lp.s1 = 1.0 / rescaling; lp.k2 = 1.0; lp.q1 = L(c_traj, 0); lp.q2 = L(q_traj, 1); lp.q1_bs = lp.q2_bs = ts;
             if (alltime) { lp.s2 = 1.0; lp.da = L(uhat, 0); lp.db = L(u_traj, 0); lp.da_bs = lp.db_bs = ts; }
-            FormGroup fg(ctx);
-            fg.chtxs_matrix(1, L(u_traj, 0), ts, L(v_traj, 0), ts, Dm, chi, eta, ctx->d_trA, batch);
-            fg.load(lp, ctx->d_trRhs, batch);
-            int r = fg.launch();
+            int r;
+            if (gw.on) {            // the same load + assemble(r'(u_n)*p_{n+1}*w*dx), in the load's place
+                ChtxsMatSpec cm;
+                cm.u = L(u_traj, 0); cm.u_bs = ts; cm.v = L(v_traj, 0); cm.v_bs = ts; cm.p0 = Dm; cm.p1 = chi; cm.p2 = eta;
+                GrowthLoadSpec gl;
+                gl.g0 = gw.r0; gl.g1 = 2.0 * gw.r1; gl.g2 = 3.0 * gw.r2; gl.e = 0;
+                gl.a = L(u_traj, 0); gl.b = L(p_traj, 1); gl.a_bs = gl.b_bs = ts;
+                gl.s1 = lp.s1 * lp.k2; gl.q1 = lp.q1; gl.q2 = lp.q2; gl.q1_bs = lp.q1_bs; gl.q2_bs = lp.q2_bs;
+                gl.s2 = lp.s2; gl.da = lp.da; gl.db = lp.db; gl.da_bs = lp.da_bs; gl.db_bs = lp.db_bs;
+                r = femfct_enqueue_chtxs_matrix_growth(ctx, 1, cm, ctx->d_trA, gl, ctx->d_trRhs, batch);
+            } else {
+                FormGroup fg(ctx);
+                fg.chtxs_matrix(1, L(u_traj, 0), ts, L(v_traj, 0), ts, Dm, chi, eta, ctx->d_trA, batch);
+                fg.load(lp, ctx->d_trRhs, batch);
+                r = fg.launch();
+            }
             if (r != FEMFCT_OK) return r;
             r = femfct_enqueue_step_ref(ctx, ctx->d_trA, nullptr, 0, make_ref(ctx->d_trRhs), n, L(p_traj, 1), ts, dt,
                                             L(p_traj, 0), ts, batch, budget);
@@ -635,6 +702,23 @@ int femfct_chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
     };
     // (diffusion / reaction terms: rows with both entries of a pair from the start: full rows)
     return femfct_run_sweep(ctx, SweepSpec{SWEEP_CHTXS_ADJOINT, num_steps, batch, num_steps - 1, true, true}, begin, step);
+}
+
+int femfct_chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat,
+                         const double* vhat, double* p_traj, double* q_traj, const double* c_traj, int32_t num_steps,
+                         double dt, const double* par, double rescaling, int32_t alltime, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return chtxs_adjoint(ctx, u_traj, v_traj, uhat, vhat, p_traj, q_traj, c_traj, num_steps, dt, par, rescaling, alltime,
+                         nullptr, batch);
+}
+
+int femfct_chtxs_adjoint_g(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat,
+                           const double* vhat, double* p_traj, double* q_traj, const double* c_traj, int32_t num_steps,
+                           double dt, const double* par, double rescaling, int32_t alltime, const double* growth,
+                           int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    return chtxs_adjoint(ctx, u_traj, v_traj, uhat, vhat, p_traj, q_traj, c_traj, num_steps, dt, par, rescaling, alltime,
+                         growth, batch);
 }
 
 // BiCGStab diagnostics of the most recent sweep that used it: info_host[step*batch + b]

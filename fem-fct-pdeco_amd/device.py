@@ -76,6 +76,13 @@ def _wind_scale(wind_scale, num_steps) -> np.ndarray:
     return ws
 
 
+def _growth(growth) -> np.ndarray:
+    g = _as_f64(growth).reshape(-1)
+    if g.size != 3:
+        raise ValueError(f"growth: {g.size} values, expected the three coefficients (r0, r1, r2) of u (r0 + r1 u + r2 u^2)")
+    return g
+
+
 def dptr(x) -> int:
     """device address of a DeviceArray / torch tensor / raw int (None -> 0)."""
     if x is None:
@@ -485,20 +492,42 @@ class Context:
                                                         int(num_steps), float(dt), _host_ptr(par), int(bool(alltime)),
                                                         int(batch)))
 
-    def chtxs_forward(self, c_level, u, v, num_steps, dt, par, rescaling=0.1, batch=1):
+    def chtxs_forward(self, c_level, u, v, num_steps, dt, par, rescaling=0.1, batch=1, growth=None):
+        """``growth=(r0, r1, r2)``: the cell equation gains the source r(u) = u (r0 + r1 u + r2 u^2), explicit in time
+        (None: no growth, the reference's solve_chtxs_system)."""
         par = _as_f64(par)
+        if growth is not None:
+            g = _growth(growth)
+            check(self.handle, lib.femfct_chtxs_forward_g(self.handle, dptr(c_level), 0, 0, dptr(u), dptr(v), int(num_steps),
+                                                          float(dt), _host_ptr(par), float(rescaling), _host_ptr(g),
+                                                          int(batch)))
+            return
         check(self.handle, lib.femfct_chtxs_forward(self.handle, dptr(c_level), dptr(u), dptr(v), int(num_steps),
                                                     float(dt), _host_ptr(par), float(rescaling), int(batch)))
 
-    def chtxs_forward_ct(self, c_traj, u, v, num_steps, dt, par, rescaling=0.1, batch=1, c_shared=False):
+    def chtxs_forward_ct(self, c_traj, u, v, num_steps, dt, par, rescaling=0.1, batch=1, c_shared=False, growth=None):
         """chtxs_forward with a per-step control: the step to level n+1 reads level n+1 of c_traj."""
         par = _as_f64(par)
+        if growth is not None:
+            g = _growth(growth)
+            check(self.handle, lib.femfct_chtxs_forward_g(self.handle, dptr(c_traj), 1, int(bool(c_shared)), dptr(u), dptr(v),
+                                                          int(num_steps), float(dt), _host_ptr(par), float(rescaling),
+                                                          _host_ptr(g), int(batch)))
+            return
         check(self.handle, lib.femfct_chtxs_forward_ct(self.handle, dptr(c_traj), int(bool(c_shared)), dptr(u), dptr(v),
                                                        int(num_steps), float(dt), _host_ptr(par), float(rescaling),
                                                        int(batch)))
 
-    def chtxs_adjoint(self, u, v, uhat, vhat, p, q, c, num_steps, dt, par, rescaling=0.1, alltime=True, batch=1):
+    def chtxs_adjoint(self, u, v, uhat, vhat, p, q, c, num_steps, dt, par, rescaling=0.1, alltime=True, batch=1,
+                      growth=None):
+        """``growth``: as in :meth:`chtxs_forward`; the p step gains the explicit load of r'(u_n) p_{n+1}."""
         par = _as_f64(par)
+        if growth is not None:
+            g = _growth(growth)
+            check(self.handle, lib.femfct_chtxs_adjoint_g(self.handle, dptr(u), dptr(v), dptr(uhat), dptr(vhat), dptr(p),
+                                                          dptr(q), dptr(c), int(num_steps), float(dt), _host_ptr(par),
+                                                          float(rescaling), int(bool(alltime)), _host_ptr(g), int(batch)))
+            return
         check(self.handle, lib.femfct_chtxs_adjoint(self.handle, dptr(u), dptr(v), dptr(uhat), dptr(vhat), dptr(p), dptr(q),
                                                     dptr(c), int(num_steps), float(dt), _host_ptr(par), float(rescaling),
                                                     int(bool(alltime)), int(batch)))

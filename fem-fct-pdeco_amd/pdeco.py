@@ -50,15 +50,20 @@ class SystemPDECO:
     FunctionSpace); host vectors are in FEniCS DoF order like the reference's."""
 
     def __init__(self, problem: str, V: SquareMeshP1, num_steps: int, dt: float, device_id: int = 0, wind=None,
-                 wind_scale=None, control_per_step=False, **overrides):
+                 wind_scale=None, control_per_step=False, growth=None, **overrides):
         """``wind`` / ``wind_scale`` (problem "schnak" only): the separable time-dependent wind ``s(t) w0(x)`` of the
         script BASELINE config 3 names (Schnak_FCT_PDECO_alltime.py:55,174-175), see systems.solve_schnak_system.
         ``control_per_step``: the state step to level n+1 reads control level n+1 (the all-time scripts, e.g.
-        Schnak_FCT_PDECO_alltime.py:182-191) instead of level 1 for every step (helpers.py:577-578 etc.)."""
+        Schnak_FCT_PDECO_alltime.py:182-191) instead of level 1 for every step (helpers.py:577-578 etc.).
+        ``growth=(r0, r1, r2)`` (problem "chtxs" only): cell growth r(u) = u (r0 + r1 u + r2 u^2) in the state and the
+        adjoint sweeps (systems.solve_chtxs_system); the gradient expression does not change."""
         if problem not in DEFAULTS:
             raise ValueError(f"unknown problem '{problem}' (one of {sorted(DEFAULTS)})")
         if (wind is not None or wind_scale is not None) and problem != "schnak":
             raise ValueError("wind / wind_scale: only the Schnakenberg driver has a time-dependent wind")
+        if growth is not None and problem != "chtxs":
+            raise ValueError("growth: only the chemotaxis driver has a growth term")
+        self.growth = growth
         self.problem, self.V, self.Nt, self.dt = problem, V, int(num_steps), float(dt)
         self.per_step = bool(control_per_step)
         self.P = dict(DEFAULTS[problem])
@@ -134,7 +139,7 @@ class SystemPDECO:
                 self.ctx.schnak_forward_ct(self.Aw, c, u, v, self.Nt, self.dt, self.par, 1.0, batch=B,
                                            wind_scale=self.wscale)
             else:
-                self.ctx.chtxs_forward_ct(c, u, v, self.Nt, self.dt, self.par, 0.1, batch=B)
+                self.ctx.chtxs_forward_ct(c, u, v, self.Nt, self.dt, self.par, 0.1, batch=B, growth=self.growth)
             return
         for b in range(B):
             clev.copy_from(c, n, dst_off=b * n, src_off=b * tl + n)
@@ -145,7 +150,7 @@ class SystemPDECO:
             # (helpers.py:1685): its defaults apply, 1 (helpers.py:512) and 1/10 (helpers.py:1252)
             self.ctx.schnak_forward(self.Aw, clev, u, v, self.Nt, self.dt, self.par, 1.0, batch=B, wind_scale=self.wscale)
         else:
-            self.ctx.chtxs_forward(clev, u, v, self.Nt, self.dt, self.par, 0.1, batch=B)
+            self.ctx.chtxs_forward(clev, u, v, self.Nt, self.dt, self.par, 0.1, batch=B, growth=self.growth)
 
     def _adjoint(self, u, v, p, q, c, tg):
         if self.problem == "nonlinear":
@@ -156,7 +161,7 @@ class SystemPDECO:
                                     alltime=self.P["optim"] == "alltime", wind_scale=self.wscale_adj)
         else:
             self.ctx.chtxs_adjoint(u, v, tg[0], tg[1], p, q, c, self.Nt, self.dt, self.par, self.P["rescaling"],
-                                   self.P["optim"] == "alltime")
+                                   self.P["optim"] == "alltime", growth=self.growth)
 
     def _cost(self, u, v, c, tg, B=1):
         return self.ctx.cost_functional(u, tg[0], c, self.Nt, self.dt, self.P["beta"], self.P["optim"],
@@ -311,8 +316,8 @@ class SystemPDECO:
 
 
 def projected_gradient_descent(problem, V, ic, targets, num_steps, dt, speculative=True, device_id=0, wind=None,
-                               wind_scale=None, control_per_step=False, **overrides):
+                               wind_scale=None, control_per_step=False, growth=None, **overrides):
     """One call = one run of the refactored driver ``problem`` (see module docstring)."""
     with SystemPDECO(problem, V, num_steps, dt, device_id=device_id, wind=wind, wind_scale=wind_scale,
-                     control_per_step=control_per_step, **overrides) as prob:
+                     control_per_step=control_per_step, growth=growth, **overrides) as prob:
         return prob.run(ic, targets, speculative=speculative)

@@ -335,9 +335,11 @@ def _chtxs_par():
 
 def solve_chtxs_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbors,
                        control_fun=None, show_plots=False, vertex_to_dof=None,
-                       generation_mode=False, output_dir=None, rescaling=1 / 10, *, control_per_step=False):
+                       generation_mode=False, output_dir=None, rescaling=1 / 10, *, control_per_step=False, growth=None):
     """helpers.py:1250-1385.  ``control_per_step``: see the module docstring
-    (chemotaxis_mimura_FCT_PGD_alltime.py:180-183; generation mode takes one control level and ignores it)."""
+    (chemotaxis_mimura_FCT_PGD_alltime.py:180-183; generation mode takes one control level and ignores it).
+    ``growth=(r0, r1, r2)`` (extension): the cell equation gains the source r(u) = u (r0 + r1 u + r2 u^2), explicit in time
+    as in mimura_data_helpers.py:65-70 -- (4, -1, 0) is m (4 - m), (0, 1, -1) is m^2 (1 - m); generation mode included."""
     if not generation_mode:
         c, per_step = _step_control(control, control_fun, nodes, num_steps, control_per_step)
     S = _system(V)
@@ -353,7 +355,7 @@ def solve_chtxs_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbo
             u0[:nodes], v0[:nodes] = var1, var2
             c_level = np.full(nodes, float(control_fun)) if control_fun is not None else np.asarray(control, dtype=float)
             u, v = B.up(u0), B.up(v0)
-            S.ctx.chtxs_forward(B.up(c_level), u, v, num_steps, dt, par, rescaling)
+            S.ctx.chtxs_forward(B.up(c_level), u, v, num_steps, dt, par, rescaling, growth=growth)
             if output_dir is not None:
                 uu, vv = B.down(u, np.empty(tl)), B.down(v, np.empty(tl))
                 t = 0
@@ -367,9 +369,9 @@ def solve_chtxs_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbo
         var2[nodes:] = np.zeros(num_steps * nodes)
         u, v = B.up(var1), B.up(var2)
         if per_step:
-            S.ctx.chtxs_forward_ct(B.up(c), u, v, num_steps, dt, par, rescaling)
+            S.ctx.chtxs_forward_ct(B.up(c), u, v, num_steps, dt, par, rescaling, growth=growth)
         else:
-            S.ctx.chtxs_forward(B.up(c), u, v, num_steps, dt, par, rescaling)
+            S.ctx.chtxs_forward(B.up(c), u, v, num_steps, dt, par, rescaling, growth=growth)
         B.down(u, var1)
         B.down(v, var2)
     finally:
@@ -379,8 +381,9 @@ def solve_chtxs_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbo
 
 def solve_adjoint_chtxs_system(uk, vk, uhat, vhat, pk, qk, control, T, V, nodes, num_steps, dt,
                                dof_neighbors, optim, show_plots=None, vertex_to_dof=None, out_folder=None,
-                               mesh=None, deltax=None, rescaling=1 / 10):
-    """helpers.py:1387-1581."""
+                               mesh=None, deltax=None, rescaling=1 / 10, *, growth=None):
+    """helpers.py:1387-1581.  ``growth``: as in :func:`solve_chtxs_system`; the p equation gains -r'(u) p, as the explicit
+    load assemble(r'(u_n)*p_{n+1}*w*dx) of the step to level n."""
     valid_options = ["alltime", "finaltime"]
     if optim not in valid_options:
         raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of {valid_options}.")
@@ -389,7 +392,7 @@ def solve_adjoint_chtxs_system(uk, vk, uhat, vhat, pk, qk, control, T, V, nodes,
     try:
         p, q = B.up(pk), B.up(qk)
         S.ctx.chtxs_adjoint(B.up(uk), B.up(vk), B.up(uhat), B.up(vhat), p, q, B.up(control), num_steps, dt,
-                            _chtxs_par(), rescaling, optim == "alltime")
+                            _chtxs_par(), rescaling, optim == "alltime", growth=growth)
         B.down(p, pk)
         B.down(q, qk)
     finally:

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct, femfct_nonlinear_adjoint_alltime, femfct_linear_trial_costs, femfct_source_trials (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
+#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct, femfct_nonlinear_adjoint_alltime, femfct_linear_trial_costs, femfct_source_trials, femfct_chtxs_{forward,adjoint}_g (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
 
 typedef struct femfct_ctx femfct_ctx;
 
@@ -387,6 +387,21 @@ int femfct_schnak_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const double
                              const double* par, double rescaling, int32_t batch);
 int femfct_chtxs_forward_ct(femfct_ctx* ctx, const double* c_traj, int32_t c_shared, double* u_traj, double* v_traj,
                             int32_t num_steps, double dt, const double* par, double rescaling, int32_t batch);
+/* Chemotaxis with cell growth (Mimura-Tsujikawa): du/dt + div(-Dm grad u + chi u exp(-eta u) grad v) = r(u),
+ * r(u) = u (r0 + r1 u + r2 u^2), growth = {r0, r1, r2}: {4, -1, 0} is m (4 - m) (chemotaxis_mimura_FCT_PGD_alltime.py, header),
+ * {0, 1, -1} is m^2 (1 - m) (mimura_data_helpers.py:70).  IMEX as the reference runs it: the FCT step from level n to n+1
+ * gets rhs = assemble(r(u_n)*v*dx), and the adjoint p step to level n gains assemble(r'(u_n)*p_{n+1}*w*dx) on its
+ * right-hand side (explicit, like the c_n q_{n+1} term); the v / q equations, the terminal conditions and the misfits are
+ * unchanged.  growth = NULL (or all three zero): exactly the sweeps above; a coefficient that is not finite is
+ * FEMFCT_ERR_INVALID.  femfct_chtxs_forward_g: c_per_step = 0: c is the frozen control level (femfct_chtxs_forward,
+ * c_shared ignored), != 0: a control trajectory (femfct_chtxs_forward_ct). */
+int femfct_chtxs_forward_g(femfct_ctx* ctx, const double* c, int32_t c_per_step, int32_t c_shared, double* u_traj,
+                           double* v_traj, int32_t num_steps, double dt, const double* par, double rescaling,
+                           const double* growth, int32_t batch);
+int femfct_chtxs_adjoint_g(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat,
+                           const double* vhat, double* p_traj, double* q_traj, const double* c_traj, int32_t num_steps,
+                           double dt, const double* par, double rescaling, int32_t alltime, const double* growth,
+                           int32_t batch);
 /* all-time misfit of the nonlinear equation (nonlinear_FCT_PDECO_alltime.py:198-216 with the HEAD operators of
  * helpers.py:1017-1037): p(T) = 0; for n = Nt-1..0:
  *   p_n = FCT_alg_ref(-Mat_p, M (uhat_n - u_n), p_{n+1}, non_flux_mat = M_u2(u_n) - M)
