@@ -56,8 +56,9 @@ __global__ void k_reduce_levels(int levels, int G, const double* __restrict__ pa
     if (threadIdx.x == 0) out[b] = (accumulate ? out[b] : 0.0) + scale * s;
 }
 
-__global__ void k_clip_axpy(int64_t count, const double* __restrict__ c, double s, const double* __restrict__ d,
-                            double lo, double hi, double* __restrict__ out) {
+// (out may alias c -- femfct.h: neither is __restrict__)
+__global__ void k_clip_axpy(int64_t count, const double* c, double s, const double* __restrict__ d, double lo, double hi,
+                            double* out) {
     int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; k < count; k += stride) out[k] = fmin(fmax(c[k] + s * d[k], lo), hi);

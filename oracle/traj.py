@@ -330,6 +330,12 @@ def solidbody_adjoint(sb: SolidBody, ck, uk, uhat, pk, nodes, num_steps, dt, opt
     return pk
 
 
+def solidbody_descent_rhs(sb: SolidBody, ck, uk, pk, beta, nodes, level):
+    """finaltime.py:233-236: -(beta*M*c + int p (b.grad u) v) of one time level, the vector ChebSI is applied to."""
+    start, end = level * nodes, (level + 1) * nodes
+    return -(beta * (sb.cm.M @ ck[start:end]) + sb.asm.drift_gradient(pk[start:end], uk[start:end], sb.drift))
+
+
 def solidbody_descent_direction(sb: SolidBody, ck, uk, pk, beta, nodes, num_steps):
     """finaltime.py:228-238: dk = ChebSI(-(beta*M*c + int p (b.grad u) v)) per level."""
     dk = np.zeros_like(ck)
@@ -337,7 +343,7 @@ def solidbody_descent_direction(sb: SolidBody, ck, uk, pk, beta, nodes, num_step
     Md = M.diagonal()
     for i in range(num_steps + 1):
         start, end = i * nodes, (i + 1) * nodes
-        rhs = -(beta * (M @ ck[start:end]) + sb.asm.drift_gradient(pk[start:end], uk[start:end], sb.drift))
+        rhs = solidbody_descent_rhs(sb, ck, uk, pk, beta, nodes, i)
         dk[start:end] = chebsi(rhs, M, Md, 20, 0.5, 2)
     return dk
 

@@ -4,7 +4,9 @@ import importlib
 
 import numpy as np
 import pytest
-from scipy.sparse import csr_matrix, diags, lil_matrix
+from scipy.sparse import csr_matrix, diags
+
+from regime_helpers import nine_point_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -18,27 +20,6 @@ def hp():
 
 def rel(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
-
-
-def nine_point_problem(N, rng):
-    """A 'mass' matrix and a flux matrix on the 9-point stencil graph of an N x N grid (ELL width 9,
-    not a P1 mesh): exercises the runtime-width kernels and the strip-fused path on a generic pattern."""
-    n = N * N
-    M = lil_matrix((n, n))
-    A = lil_matrix((n, n))
-    for iy in range(N):
-        for ix in range(N):
-            i = iy * N + ix
-            for dy in (-1, 0, 1):
-                for dx in (-1, 0, 1):
-                    jx, jy = ix + dx, iy + dy
-                    if 0 <= jx < N and 0 <= jy < N:
-                        j = jy * N + jx
-                        M[i, j] = 4.0 if i == j else 0.25 + 0.1 * ((i + j) % 3)
-                        A[i, j] = rng.standard_normal() * (1.0 if i != j else 0.3)
-    M = csr_matrix(M)
-    M = (M + M.T) * 0.5
-    return csr_matrix(M), csr_matrix(A)
 
 
 @pytest.mark.parametrize("N", [6, 23])

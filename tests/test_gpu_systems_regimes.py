@@ -19,25 +19,19 @@ moves it, see _regime_knobs_default), runs every sweep of one system on B member
 members with the oracle (all of them for B <= 8, else the first, middle and last one) and with the same member run
 alone (another regime for B > 1: the solver tolerance, not bits), and checks the solver logs."""
 import importlib
-import os
 
 import numpy as np
 import pytest
 
 import nonlinear_alltime_oracle as na
 import per_step_oracle as pso
+from regime_helpers import REGIME_KNOBS, regime_knobs_default as _regime_knobs_default  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 STATE_TOL, ADJ_TOL, MEMBER_TOL = 1e-10, 1e-9, 1e-12
 DT = {"nonlinear": 1e-3, "schnak": 5e-4, "chtxs": 5e-4}
 
-
-# tuning knobs that move a size class to other kernels (or the species solve to BiCGStab): the regime and Chebyshev
-# assertions hold for their defaults; the oracle comparisons hold whatever they are set to
-REGIME_KNOBS = ("FEMFCT_TILES", "FEMFCT_STRIPS", "FEMFCT_IMPLICIT", "FEMFCT_TILE4", "FEMFCT_T4_DPP", "FEMFCT_T4_K",
-                "FEMFCT_T4_WALK", "FEMFCT_MESH_SOLVE", "FEMFCT_SINGLE_PATCH_BATCH", "FEMFCT_SPECIES_SOLVER",
-                "FEMFCT_DEEP_HALO", "FEMFCT_WG_SLOTS", "FEMFCT_STRIP_K", "FEMFCT_MESH_STEP_BATCH_LARGE")
 
 CASES = [
     pytest.param(46, 1, "TILE32", {}, id="N46-B1"),
@@ -71,10 +65,6 @@ def rel(a, b):
 
 def _report(name, **errs):
     print(f"[regimes] {name}: " + ", ".join(f"{k}={v:.3e}" for k, v in errs.items()))
-
-
-def _regime_knobs_default():
-    return not any(k in os.environ for k in REGIME_KNOBS)
 
 
 def _num_steps(N):
