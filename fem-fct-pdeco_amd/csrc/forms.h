@@ -37,6 +37,15 @@ struct ReactLoadSpec {
     int64_t a_bs = 0, b_bs = 0, g_bs = 0, x_bs = 0;
 };
 
+// out = (theta/dt) * Mw(w) (a - b) - Mg(g) x   (kernels_obs.hip: the load of an adjoint step that tracks snapshots;
+// theta: the level's weight, read on the device; w absent: Mw = M; g absent: no reaction term; g, w shared by the batch)
+struct ObsLoadSpec {
+    VecRef a{nullptr, nullptr, 0, 0}, b{nullptr, nullptr, 0, 0}, theta{nullptr, nullptr, 0, 0}, w{nullptr, nullptr, 0, 0},
+        g{nullptr, nullptr, 0, 0}, x{nullptr, nullptr, 0, 0};
+    int64_t a_bs = 0, b_bs = 0, x_bs = 0;
+    double dt = 1.0;
+};
+
 // out_i = s1 * int q1 q2 phi_i + s2*(da_i - db_i) + int (g0 + g1*a + g2*a^2) a^e b phi_i   (kernels_growth.hip: the growth
 // term of the chemotaxis system; b absent: 1, q1 / da absent: no such term)
 struct GrowthLoadSpec {
@@ -80,6 +89,9 @@ MeshArgs femfct_mesh_args(const femfct_ctx* ctx);
 int femfct_enqueue_weighted_mass(femfct_ctx* ctx, const WMassSpec& sp, double* out, int32_t batch);
 int femfct_enqueue_load(femfct_ctx* ctx, const LoadSpec& sp, double* out, int32_t batch);
 int femfct_enqueue_react_load(femfct_ctx* ctx, const ReactLoadSpec& sp, double* out, int32_t batch);
+int femfct_enqueue_obs_load(femfct_ctx* ctx, const ObsLoadSpec& sp, double* out, int32_t batch);
+int femfct_enqueue_obs_terminal(femfct_ctx* ctx, double tau, const double* window, const double* uhat, int64_t uhat_bs,
+                                const double* u, int64_t u_bs, double* p, int64_t p_bs, int32_t batch);
 int femfct_enqueue_chtxs_matrix(femfct_ctx* ctx, int adjoint, VecRef u, int64_t u_bs, VecRef v, int64_t v_bs,
                                 double Dm, double chi, double eta, double* out, int32_t batch);
 int femfct_enqueue_growth_load(femfct_ctx* ctx, const GrowthLoadSpec& sp, double* out, int32_t batch);

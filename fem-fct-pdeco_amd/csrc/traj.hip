@@ -241,15 +241,27 @@ static int solidbody_forward_sweep(femfct_ctx* ctx, const double* Arot_ell, cons
     return femfct_run_sweep(ctx, SweepSpec{SWEEP_SOLIDBODY_FORWARD, num_steps, batch, 0, false, g_traj || eps != 0.0}, begin, step);
 }
 
+// Snapshot tracking (kernels_obs.hip): J = 1/2 sum_n theta_n ||u_n - uhat_n||^2_Mw + tau/2 ||u_Nt - uhat_Nt||^2.  theta:
+// num_steps + 1 weights on the device, read per level through the level counter; window (may be null): nodal omega >= 0.
+struct ObsArgs {
+    const double* theta;
+    double tau;
+    const double* window;
+};
+
 // g_traj (may be null): rhs_n = [M (uhat_n - u_n)] - Mg(g_n) p_{n+1}, the coefficient at the level being produced
 // (advection_FCT_PDECO_finaltime_exact.py:317-321); the final-time sweep has a right-hand side then, too
+// obs (may be null; `alltime` is unused with it): uhat is a trajectory, p_Nt = tau omega (uhat_Nt - u_Nt) and
+// rhs_n = (theta_n/dt) Mw (uhat_n - u_n) [- Mg(g_n) p_{n+1}]: the two modes above are (tau, theta) = (1, 0) and (0, dt)
 static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
                                    const double* g_traj, const double* u_traj, const double* uhat, double* p_traj,
                                    int32_t num_steps, double dt, double eps, double rot_scale, double bx, double by,
-                                   int32_t alltime, int32_t batch) {
+                                   int32_t alltime, int32_t batch, const ObsArgs* obs = nullptr) {
     FEMFCT_ENTER(ctx);
     ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
     ARG_TRY(ctx, c_traj && u_traj && uhat && p_traj && num_steps >= 1 && dt > 0 && batch >= 1, "bad argument");
+    ARG_TRY(ctx, !obs || obs->theta, "theta is null");
+    ARG_TRY(ctx, !obs || obs->tau >= 0.0, "tau must be >= 0");
     ARG_TRY(ctx, Arot_ell || rot_scale == 0.0, "Arot_ell is required when rot_scale != 0");
     int rc = femfct_ensure_traj_ws(ctx, batch, num_steps);
     if (rc != FEMFCT_OK) return rc;
@@ -270,6 +282,15 @@ static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, cons
             pre = solidbody_preassemble(ctx, Arot, c_traj, c_shared, tstride, 0, eps, +1.0, rot_scale, bx, by, num_steps,
                                         batch, dt, &Aall);
         // terminal condition: p(T) = uhat_T - u(T) (finaltime.py:201) or 0 (alltime.py:232)
+        if (obs) {      // p(T) = tau omega (uhat_T - u(T)); tau = 0: uhat_T is not read
+            double* pT = p_traj + (int64_t)num_steps * n;
+            if (obs->tau == 0.0)
+                for (int32_t b = 0; b < batch; ++b) HIP_TRY(ctx, hipMemsetAsync(pT + b * tstride, 0, sizeof(double) * n, ctx->stream));
+            else
+                femfct_enqueue_obs_terminal(ctx, obs->tau, obs->window, uhat + (int64_t)num_steps * n, tstride,
+                                            u_traj + (int64_t)num_steps * n, tstride, pT, tstride, batch);
+            return FEMFCT_OK;
+        }
         for (int32_t b = 0; b < batch; ++b) {
             double* pT = p_traj + b * tstride + (int64_t)num_steps * n;
             if (alltime) HIP_TRY(ctx, hipMemsetAsync(pT, 0, sizeof(double) * n, ctx->stream));
@@ -283,6 +304,12 @@ static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, cons
                                  key_bits(rot_scale), key_bits(bx), key_bits(by), key_bits(alltime), key_bits(batch),
                                  key_bits((int32_t)budget), key_bits(ctx->rel_tol), key_bits(pre ? Aall.base : nullptr),
                                  key_bits((int32_t)inl), key_bits((int32_t)rotg), key_bits(rot_om), key_bits(g_traj)};
+        if (obs) {      // another load kernel is captured, with these arguments
+            key.push_back(key_bits(obs->theta));
+            key.push_back(key_bits(obs->tau));
+            key.push_back(key_bits(obs->window));
+            key.push_back(key_bits((int32_t)1));
+        }
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             // level counter = n: control c_n (finaltime.py:213), p_{n+1} -> p_n
             MatRef A = Aall;
@@ -295,7 +322,20 @@ static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, cons
                 A = MatRef{ctx->d_trA, nullptr, 0, 0, (int64_t)ctx->W * n};
             }
             VecRef rhs = make_ref(nullptr);
-            if (g_traj) {   // coefficient at level n, adjoint at level n+1; all-time: the misfit load in the same launch
+            if (obs) {      // the weighted misfit of level n (and the reaction term) in the load launch of the all-time step
+                ObsLoadSpec ol;
+                ol.a = lref(ctx, uhat, lv, n, 0);   ol.a_bs = tstride;
+                ol.b = lref(ctx, u_traj, lv, n, 0); ol.b_bs = tstride;
+                ol.theta = lref(ctx, obs->theta, lv, 1, 0);
+                ol.w = make_ref(obs->window);
+                ol.dt = dt;
+                if (g_traj) {
+                    ol.g = lref(ctx, g_traj, lv, n, 0);
+                    ol.x = lref(ctx, p_traj, lv, n, 1); ol.x_bs = tstride;
+                }
+                femfct_enqueue_obs_load(ctx, ol, ctx->d_trRhs, batch);
+                rhs = make_ref(ctx->d_trRhs);
+            } else if (g_traj) {   // coefficient at level n, adjoint at level n+1; all-time: the misfit load in the same launch
                 ReactLoadSpec rl;
                 if (alltime) {
                     rl.a = lref(ctx, uhat, lv, n, 0);   rl.a_bs = tstride;
@@ -384,6 +424,32 @@ int femfct_linear_adjoint_react(femfct_ctx* ctx, const double* Aadj_ell, const d
     if (rc != FEMFCT_OK) return rc;
     return solidbody_adjoint_sweep(ctx, Aadj_ell, zc, 1, g_traj, u_traj, uhat, p_traj, num_steps, dt, eps, 1.0, 0.0, 0.0,
                                    alltime, batch);
+}
+
+// Adjoint sweeps that track the state at chosen time levels (snapshot observations; added after ABI version 5, backward
+// compatible): see ObsArgs.  (tau, theta) = (1, 0) and (0, dt) enqueue the arithmetic of alltime = 0 and 1.
+int femfct_solidbody_adjoint_obs(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                                 const double* u_traj, const double* uhat_traj, const double* theta, double tau,
+                                 const double* window, double* p_traj, int32_t num_steps, double dt, double eps,
+                                 double rot_scale, double bx, double by, int32_t batch) {
+    const ObsArgs obs{theta, tau, window};
+    return solidbody_adjoint_sweep(ctx, Arot_ell, c_traj, c_shared, nullptr, u_traj, uhat_traj, p_traj, num_steps, dt, eps,
+                                   rot_scale, bx, by, 0, batch, &obs);
+}
+
+int femfct_linear_adjoint_react_obs(femfct_ctx* ctx, const double* Aadj_ell, const double* g_traj, const double* u_traj,
+                                    const double* uhat_traj, const double* theta, double tau, const double* window,
+                                    double* p_traj, int32_t num_steps, double dt, double eps, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
+    ARG_TRY(ctx, theta, "theta is null");
+    ARG_TRY(ctx, Aadj_ell && g_traj && u_traj && uhat_traj && p_traj && num_steps >= 1 && batch >= 1, "bad argument");
+    const double* zc = nullptr;
+    int rc = zero_control(ctx, num_steps, &zc);
+    if (rc != FEMFCT_OK) return rc;
+    const ObsArgs obs{theta, tau, window};
+    return solidbody_adjoint_sweep(ctx, Aadj_ell, zc, 1, g_traj, u_traj, uhat_traj, p_traj, num_steps, dt, eps, 1.0, 0.0, 0.0,
+                                   0, batch, &obs);
 }
 
 // per-step solver diagnostics of the most recent trajectory sweep: info[step*batch + b]

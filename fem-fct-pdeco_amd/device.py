@@ -355,6 +355,35 @@ class Context:
         """out = M src - Mg(g) x for one level, matrix-free (``src`` may be None); ``g`` is shared by the batch."""
         check(self.handle, lib.femfct_react_load(self.handle, dptr(src), dptr(g), dptr(x), dptr(out), int(batch)))
 
+    # -- snapshot observations: J = 1/2 sum_n w_n (u_n - uhat_n)^T Mw (u_n - uhat_n), Mw = assemble(omega_h*u*v*dx) -------
+    def solidbody_adjoint_obs(self, Arot, c_traj, u_traj, uhat_traj, theta, tau, window, p_traj, num_steps, dt, eps=0.0,
+                              rot_scale=1.0, drift=(1.0, 1.0), batch=1, c_shared=False):
+        """Adjoint sweep tracking the state at chosen levels: p_Nt = tau * omega .* (uhat_Nt - u_Nt), load
+        (theta[n]/dt) Mw (uhat_n - u_n).  ``theta``: num_steps + 1 device doubles; ``window``: n device doubles or None."""
+        check(self.handle, lib.femfct_solidbody_adjoint_obs(
+            self.handle, dptr(Arot), dptr(c_traj), int(bool(c_shared)), dptr(u_traj), dptr(uhat_traj), dptr(theta),
+            float(tau), dptr(window), dptr(p_traj), int(num_steps), float(dt), float(eps), float(rot_scale),
+            float(drift[0]), float(drift[1]), int(batch)))
+
+    def linear_adjoint_react_obs(self, Aadj, g_traj, u_traj, uhat_traj, theta, tau, window, p_traj, num_steps, dt, eps,
+                                 batch=1):
+        """The same for the sweep with the explicit reaction term (load ... - Mg(g_n) p_{n+1})."""
+        check(self.handle, lib.femfct_linear_adjoint_react_obs(
+            self.handle, dptr(Aadj), dptr(g_traj), dptr(u_traj), dptr(uhat_traj), dptr(theta), float(tau), dptr(window),
+            dptr(p_traj), int(num_steps), float(dt), float(eps), int(batch)))
+
+    def obs_load(self, a, b, theta, level, dt, out, window=None, batch=1):
+        """out = (theta[level]/dt) Mw (a - b) for one level (zeros, a and b unread, where theta[level] == 0)."""
+        check(self.handle, lib.femfct_obs_load(self.handle, dptr(a), dptr(b), dptr(theta), int(level), float(dt),
+                                               dptr(window), dptr(out), int(batch)))
+
+    def obs_cost(self, u_traj, uhat_traj, cost_w, num_steps, window=None, batch=1) -> np.ndarray:
+        """1/2 sum_n cost_w[n] (u_n - uhat_n)^T Mw (u_n - uhat_n) per batch member (``cost_w``: device doubles)."""
+        out = np.empty(batch)
+        check(self.handle, lib.femfct_obs_cost(self.handle, dptr(u_traj), dptr(uhat_traj), dptr(cost_w), dptr(window),
+                                               int(num_steps), int(batch), _host_ptr(out)))
+        return out
+
     def assemble_weighted_mass(self, f, out: DeviceArray | None = None) -> DeviceArray:
         """``assemble_sparse(f_h*u*v*dx)`` for the P1 function with the nodal values ``f`` (ELL)."""
         if out is None:

@@ -34,6 +34,98 @@ def rotation_wind(om):
     return lambda x, y: (-(1.0 / om) * y, (1.0 / om) * x)
 
 
+OPTIMS = ("alltime", "finaltime", "snapshots")
+
+
+class Observations:
+    """Observations of a state at chosen time levels, the tracking term
+
+        J = 1/2 sum_n w_n (u_n - uhat_n)^T Mw (u_n - uhat_n),      Mw = assemble(omega_h*u*v*dx)  (M without a window)
+
+    ``levels``: strictly increasing integer time levels in 1..num_steps; ``weights``: one w_n >= 0 per level (default 1);
+    ``window``: nodal values omega >= 0 of a P1 field in the problem's DoF order that restricts or weights the observed
+    part of the domain (None: omega = 1).  Derived, as the adjoint sweep and the cost take them:
+
+        theta[n]   weight of level n < num_steps, 0 elsewhere (num_steps + 1 values): the step to level n is loaded with
+                   (theta[n]/dt) Mw (uhat_n - u_n), the discrete adjoint of the backward-Euler step for J
+        tau        weight of level num_steps (0 if not observed): p_Nt = tau * omega .* (uhat_Nt - u_Nt), nodal as the
+                   reference's terminal condition
+        cost_w[n]  the weights including level num_steps
+
+    The reference's two modes are :meth:`finaltime` and :meth:`alltime`."""
+
+    def __init__(self, num_steps, levels, weights=None, window=None):
+        Nt = int(num_steps)
+        if Nt < 1:
+            raise ValueError(f"num_steps = {num_steps}: must be >= 1")
+        lv = np.asarray(levels)
+        if lv.ndim != 1 or lv.size == 0:
+            raise ValueError("no observed levels")
+        if not np.all(lv == np.floor(lv)):
+            raise ValueError("levels must be integers")
+        lv = lv.astype(np.int64)
+        if lv.min() < 1 or lv.max() > Nt:
+            raise ValueError(f"levels must lie in 1..num_steps = {Nt}")
+        if np.any(np.diff(lv) <= 0):
+            raise ValueError("levels must be strictly increasing (sorted, no duplicates)")
+        w = np.ones(lv.size) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
+        if w.size != lv.size:
+            raise ValueError(f"{w.size} weights for {lv.size} levels")
+        if not np.all(w >= 0):
+            raise ValueError("weights must be >= 0")
+        cost_w = np.zeros(Nt + 1)
+        cost_w[lv] = w
+        theta = cost_w.copy()
+        theta[Nt] = 0.0
+        self._set(Nt, lv, theta, float(cost_w[Nt]), cost_w, window)
+
+    def _set(self, Nt, levels, theta, tau, cost_w, window):
+        if window is not None:
+            window = np.array(window, dtype=np.float64).ravel()
+            if not np.all(window >= 0):
+                raise ValueError("window must be >= 0 everywhere")
+            window.setflags(write=False)
+        self.num_steps, self.levels, self.theta, self.tau, self.cost_w, self.window = Nt, levels, theta, tau, cost_w, window
+        for a in (levels, theta, cost_w):
+            a.setflags(write=False)
+
+    @classmethod
+    def finaltime(cls, num_steps, window=None):
+        """The final-time mode: tau = 1, theta = 0."""
+        return cls(num_steps, [int(num_steps)], window=window)
+
+    @classmethod
+    def alltime(cls, num_steps, dt, window=None):
+        """The all-time mode: tau = 0 and theta[n] = dt at every level n < num_steps, level 0 included (the reference's
+        sweep loads it); the cost weights are the trapezoid of L2_norm_sq_Q (helpers.py:330-360)."""
+        Nt = int(num_steps)
+        if Nt < 1 or not dt > 0:
+            raise ValueError("num_steps >= 1 and dt > 0 are required")
+        theta = np.full(Nt + 1, float(dt))
+        theta[Nt] = 0.0
+        cost_w = np.full(Nt + 1, float(dt))
+        cost_w[0] = cost_w[Nt] = 0.5 * dt
+        self = cls.__new__(cls)
+        self._set(Nt, np.arange(0, Nt + 1), theta, 0.0, cost_w, window)
+        return self
+
+    def check(self, num_steps, nodes):
+        """Raises ValueError unless these observations fit a problem of ``num_steps`` steps and ``nodes`` DoFs."""
+        if self.num_steps != int(num_steps):
+            raise ValueError(f"observations of {self.num_steps} steps for a problem of {num_steps}")
+        if self.window is not None and self.window.size != int(nodes):
+            raise ValueError(f"window of {self.window.size} values, expected {nodes}")
+        return self
+
+
+def _need_obs(optim, obs):
+    if optim not in OPTIMS:
+        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of {list(OPTIMS)}.")
+    if optim == "snapshots" and not isinstance(obs, Observations):
+        raise ValueError("optim='snapshots' needs obs=Observations(...)")
+    return optim == "snapshots"
+
+
 class SolidBodyDrift:
     """Drift-control advection problem on one GPU; ``batch`` independent trajectories advance
     together in every kernel launch (Armijo trial steps, regularisation sweeps)."""
@@ -65,9 +157,25 @@ class SolidBodyDrift:
         self.ctx.solidbody_forward(self.Arot, c, u, self.num_steps, self.dt, self.eps, self.rot_scale,
                                    self.drift, self.batch if batch is None else batch, c_shared, src_traj=src)
 
-    def adjoint(self, c, u, uhat, p, optim="finaltime", batch=None, c_shared=False):
-        if optim not in ("alltime", "finaltime"):
-            raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+    def obs_device(self, obs: Observations):
+        """``(theta, cost_w, window)`` of ``obs`` on the device (uploaded once per Observations object)."""
+        cache = self.__dict__.setdefault("_obs_cache", {})
+        hit = cache.get(id(obs))
+        if hit is None or hit[0] is not obs:
+            obs.check(self.num_steps, self.n)
+            hit = (obs, self.ctx.array(obs.theta), self.ctx.array(obs.cost_w),
+                   None if obs.window is None else self.ctx.array(obs.window))
+            cache[id(obs)] = hit
+        return hit[1:]
+
+    def adjoint(self, c, u, uhat, p, optim="finaltime", batch=None, c_shared=False, obs=None):
+        """optim="snapshots": ``uhat`` is a trajectory read at the levels ``obs`` observes only."""
+        if _need_obs(optim, obs):
+            theta, _, window = self.obs_device(obs)
+            self.ctx.solidbody_adjoint_obs(self.Arot, c, u, uhat, theta, obs.tau, window, p, self.num_steps, self.dt,
+                                           self.eps, self.rot_scale, self.drift, self.batch if batch is None else batch,
+                                           c_shared)
+            return
         self.ctx.solidbody_adjoint(self.Arot, c, u, uhat, p, self.num_steps, self.dt, self.eps, self.rot_scale,
                                    self.drift, optim == "alltime", self.batch if batch is None else batch, c_shared)
 
@@ -84,7 +192,12 @@ class SolidBodyDrift:
             if own:
                 rhs.free()
 
-    def cost(self, u, target, c, beta, optim, batch=None):
+    def cost(self, u, target, c, beta, optim, batch=None, obs=None):
+        if _need_obs(optim, obs):       # every member (all Armijo trials of a batched sweep) in one call
+            B = self.batch if batch is None else batch
+            _, cost_w, window = self.obs_device(obs)
+            return (self.ctx.obs_cost(u, target, cost_w, self.num_steps, window, batch=B)
+                    + beta / 2 * self.ctx.l2_norm_sq_Q(c, None, self.num_steps, self.dt, batch=B))
         return self.ctx.cost_functional(u, target, c, self.num_steps, self.dt, beta, optim,
                                         batch=self.batch if batch is None else batch)
 
@@ -101,14 +214,14 @@ class SolidBodyDrift:
             u.free()
         return uk
 
-    def solve_adjoint(self, ck, uk, uhat, pk, optim="finaltime"):
+    def solve_adjoint(self, ck, uk, uhat, pk, optim="finaltime", obs=None):
         """finaltime.py:200-221 / alltime.py:232-259: fills and returns ``pk``."""
         c = self.ctx.array(ck)
         u = self.ctx.array(uk)
         uh = self.ctx.array(uhat)
         p = self.ctx.zeros(self.tlen)
         try:
-            self.adjoint(c, u, uh, p, optim, batch=1)
+            self.adjoint(c, u, uh, p, optim, batch=1, obs=obs)
             p.download(pk)
         finally:
             for a in (c, u, uh, p):
@@ -147,9 +260,9 @@ class LinearSourceControl(SolidBodyDrift):
         """advection_FCT_PDECO_alltime_exact.py:236-253 (src = g + c, both trajectories)"""
         self.forward(self._zero_c, u, batch=batch, c_shared=True, src=src)
 
-    def adjoint_state(self, u, uhat, p, optim="alltime", batch=None):
+    def adjoint_state(self, u, uhat, p, optim="alltime", batch=None, obs=None):
         """:259-274 (all-time) / advection_FCT_PDECO_finaltime.py (final-time)"""
-        self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True)
+        self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True, obs=obs)
 
     def descent_direction(self, c, p, beta, d):
         """advection_FCT_PDECO_alltime_exact.py:278: d = -(beta*c - p), every level, the script's operation order."""
@@ -170,10 +283,10 @@ class LinearSourceControl(SolidBodyDrift):
             u.free()
         return uk
 
-    def solve_adjoint_state(self, uk, uhat, pk, optim="alltime"):
+    def solve_adjoint_state(self, uk, uhat, pk, optim="alltime", obs=None):
         u, uh, p = self.ctx.array(uk), self.ctx.array(uhat), self.ctx.zeros(self.tlen)
         try:
-            self.adjoint_state(u, uh, p, optim, batch=1)
+            self.adjoint_state(u, uh, p, optim, batch=1, obs=obs)
             p.download(pk)
         finally:
             for a in (u, uh, p):
@@ -222,9 +335,12 @@ class LinearReactionSourceControl(LinearSourceControl):
         self.ctx.linear_forward_react(self.Arot, src, self._react, u, self.num_steps, self.dt, self.eps,
                                       self.batch if batch is None else batch)
 
-    def adjoint_state(self, u, uhat, p, optim="finaltime", batch=None):
-        if optim not in ("alltime", "finaltime"):
-            raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+    def adjoint_state(self, u, uhat, p, optim="finaltime", batch=None, obs=None):
+        if _need_obs(optim, obs):
+            theta, _, window = self.obs_device(obs)
+            self.ctx.linear_adjoint_react_obs(self.Aadj, self._react, u, uhat, theta, obs.tau, window, p, self.num_steps,
+                                              self.dt, self.eps, self.batch if batch is None else batch)
+            return
         self.ctx.linear_adjoint_react(self.Aadj, self._react, u, uhat, p, self.num_steps, self.dt, self.eps,
                                       optim == "alltime", self.batch if batch is None else batch)
 
@@ -278,8 +394,16 @@ def pgd_solidbody_alltime(prob: SolidBodyDrift, u0, uhat_all, c0, beta, c_lower,
                          optim="alltime")
 
 
+def pgd_solidbody_snapshots(prob: SolidBodyDrift, u0, uhat, obs: Observations, c0, beta, c_lower, c_upper, iters,
+                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None):
+    """Snapshot variant of :func:`pgd_solidbody`: ``uhat`` is a (num_steps+1)*n trajectory of which only the levels that
+    ``obs`` observes are read (the others may hold anything, NaN included)."""
+    return pgd_solidbody(prob, u0, uhat, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
+                         optim="snapshots", obs=obs)
+
+
 def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters,
-                  gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, optim="finaltime"):
+                  gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None):
     """Projected gradient descent for the drift-control problem, following the loop of
     advection_solidbody_FCT_PDECO_finaltime_Garvie.py:164-330 / ..._alltime_Garvie.py:164-340 step for step:
 
@@ -294,10 +418,11 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     ``max_armijo`` trial steps as one batch of independent trajectories (same launches, B = max_armijo)
     and picks the first accepted one -- the iterate of the sequential search (each trial trajectory is
     the same computation; the states agree to the low-order solver tolerance, 1e-13).
+    optim="snapshots": target trajectory read at the levels of ``obs`` only, the adjoint and cost of
+    :class:`Observations`; u is seeded with the target at the observed levels (both modes above, seen as observations).
     Returns ``(u, p, c, history)`` as NumPy arrays + a dict of per-iteration scalars."""
-    if optim not in ("alltime", "finaltime"):
-        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
-    alltime = optim == "alltime"
+    snap = _need_obs(optim, obs)
+    alltime = optim == "alltime" or snap         # (the target is a trajectory)
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     B = int(max_armijo) if speculative else 1
     u = ctx.zeros(tl)
@@ -319,17 +444,20 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     # its threshold relative to the cost, (J_trial - J_k + gam/s ||c_inc - c||^2_Q) / |J_k|  (> 0: rejected).  A margin of
     # the size of the solver tolerance would mean that two faithful implementations may decide differently.
     hist = dict(cost=[], armijo_k=[], step=[], rel_change=[], armijo_margin=[], wall=[], wall0=time.perf_counter())
-    if alltime:
+    if snap:
+        for lv in obs.levels[obs.levels > 0]:
+            u.copy_from(uh, n, dst_off=int(lv) * n, src_off=int(lv) * n)
+    elif alltime:
         u.copy_from(uh, tl - n, dst_off=n, src_off=n)      # uk = np.copy(uhat_all), level 0 = u0
     else:
         u.copy_from(uh, n, dst_off=Nt * n)                 # uk[num_steps*nodes:] = uhat_T
     try:
         for it in range(iters):
-            prob.adjoint(c_prev, u, uh, p, optim, batch=1)
+            prob.adjoint(c_prev, u, uh, p, optim, batch=1, obs=obs)
             prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs)
             ctx.project_control(c_prev, s0, d, c_lower, c_upper, c, tl)
             prob.forward(c, u, batch=1)
-            J_k = float(prob.cost(u, uh, c, beta, optim, batch=1)[0])
+            J_k = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs)[0])
             svals = [s0 * (1 / 2 ** k) for k in range(max_armijo)]
             accepted = None
             if speculative:
@@ -337,7 +465,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
                     ctx.project_control(c, s, d, c_lower, c_upper, cB.ptr + 8 * k * tl, tl)
                     ckB.copy_from(c, tl, dst_off=k * tl)
                 prob.forward(cB, uB, batch=B)
-                J = prob.cost(uB, uhB, cB, beta, optim, batch=B)
+                J = prob.cost(uB, uhB, cB, beta, optim, batch=B, obs=obs)
                 stat = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=B)
                 margins = []
                 for k, s in enumerate(svals):
@@ -354,7 +482,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
                     accepted = k
                     ctx.project_control(c, s, d, c_lower, c_upper, cB, tl)
                     prob.forward(cB, uB, batch=1)
-                    J_acc = float(prob.cost(uB, uh, cB, beta, optim, batch=1)[0])
+                    J_acc = float(prob.cost(uB, uh, cB, beta, optim, batch=1, obs=obs)[0])
                     stat = float(ctx.l2_norm_sq_Q(cB, c, Nt, dt)[0])
                     margins.append((J_acc - J_k + gam / s * stat) / abs(J_k))
                     if not (J_acc - J_k > -gam / s * stat):
@@ -377,7 +505,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
 
 
 def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
-                       increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both"):
+                       increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None):
     """Projected gradient descent for the linear source-control problem, the loop of
     advection_FCT_PDECO_alltime_exact.py:212-330 (optim="alltime", stop="both") and advection_FCT_PDECO_finaltime.py:
     170-280 (optim="finaltime", stop="cost"):
@@ -393,22 +521,26 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
     ||c_k|| = 0) and stop_crit2 = |J_ref - J_acc| / |J_ref|; the loop runs while stop_crit2 >= tol, or (stop="both")
     stop_crit >= tol, and fewer than ``max_iters`` iterations have run.
 
+    optim="snapshots" (increment="resolve" only): the adjoint and cost of ``obs``, an :class:`Observations`; ``uhat`` is
+    a trajectory read at the observed levels only.
     ``uhat``: target trajectory (all-time) or uhat_T (final-time, n values); ``g``: fixed source trajectory or None.
     Everything stays in HBM; the host sees scalars only.  Returns ``(u, p, c, hist)`` like the scripts: u and p are the
     last iteration's state and adjoint (at the control that iteration started from), c the last accepted control.
     hist["cost"][k] is the accepted J_acc (the linear estimate in linear mode); hist["cost_state"][k] the cost
     J(S(g + c_k), c_k) of the re-solved state at the control iteration k started from, so hist["cost_state"][k + 1]
     re-solves hist["cost"][k]."""
-    if optim not in ("alltime", "finaltime"):
-        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+    snap = _need_obs(optim, obs)
     if increment not in ("linear", "resolve"):
         raise ValueError(f"Invalid value for 'increment': '{increment}'. Must be one of ['linear', 'resolve'].")
+    if snap and increment == "linear":
+        raise ValueError("optim='snapshots' needs increment='resolve': the fused linear-increment trial costs know the "
+                         "all-time and final-time modes only")
     if stop not in ("both", "cost"):
         raise ValueError(f"Invalid value for 'stop': '{stop}'. Must be one of ['both', 'cost'].")
     K = int(max_armijo)
     if not 1 <= K <= _lib.MAX_TRIALS:
         raise ValueError(f"max_armijo = {K}: must be in 1..{_lib.MAX_TRIALS}")
-    alltime, linear = optim == "alltime", increment == "linear"
+    alltime, linear = optim == "alltime" or snap, increment == "linear"
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     uhat = np.asarray(uhat, dtype=np.float64).ravel()
     if uhat.size != (tl if alltime else n):
@@ -442,7 +574,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             for k in range(K):
                 uB.copy_from(u, n, dst_off=k * tl)              # level 0 of every trial state = u0
                 uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
-        cost = lambda uu, cc: float(prob.cost(uu, uh, cc, beta, optim, batch=1)[0])
+        cost = lambda uu, cc: float(prob.cost(uu, uh, cc, beta, optim, batch=1, obs=obs)[0])
         J_ref = 10 * cost(u, c)                                 # alltime_exact.py:212 / finaltime.py:170
         hist = dict(cost=[], cost_state=[], armijo_k=[], step=[], stop_crit=[], stop_crit2=[], armijo_margin=[],
                     wall=[], wall0=time.perf_counter())
@@ -453,7 +585,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
                 ctx.axpby(tl, 1.0, gd, 1.0, c, src)
             prob.state(src, u, batch=1)
             hist["cost_state"].append(cost(u, c))
-            prob.adjoint_state(u, uh, p, optim, batch=1)
+            prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs) if snap else prob.adjoint_state(u, uh, p, optim, batch=1)
             prob.descent_direction(c, p, beta, d)
             if linear:
                 prob.sensitivity(d, w)
@@ -461,7 +593,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             else:
                 ctx.source_trials(c, d, s0, K, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
                 prob.state(srcB, uB, batch=K)
-                J = prob.cost(uB, uhB, cB, beta, optim, batch=K)
+                J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs)
                 for k in range(K):
                     ckB.copy_from(c, tl, dst_off=k * tl)
                 dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=K)

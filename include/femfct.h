@@ -261,6 +261,30 @@ int femfct_linear_adjoint_react(femfct_ctx* ctx, const double* Aadj_ell, const d
  * NULL: no M src term), x and out are n doubles per batch member */
 int femfct_react_load(femfct_ctx* ctx, const double* src_dev, const double* g_dev, const double* x_dev, double* out_dev,
                       int32_t batch);
+/* Tracking the state at chosen time levels (snapshot observations; added after ABI version 5, backward compatible):
+ *   J = 1/2 sum_n w_n (u_n - uhat_n)^T Mw (u_n - uhat_n),  Mw = assemble(omega_h*u*v*dx), = M without a window.
+ * The adjoint sweep ends in p_Nt = tau * omega .* (uhat_Nt - u_Nt) (nodal; not read if tau == 0) and loads the step to
+ * level n with (theta[n]/dt) Mw (uhat_n - u_n).  uhat_traj: (num_steps + 1)*n doubles per batch member, read at the levels
+ * of non-zero weight only.  theta: num_steps + 1 doubles ON THE DEVICE, owned by the caller (theta[num_steps] unused: tau
+ * is that level's weight).  window: n doubles on the device, omega >= 0 in the problem's DoF order, or NULL (omega = 1).
+ * (tau, theta) = (1, 0) and (0, dt) are femfct_solidbody_adjoint with alltime = 0 and 1, bit for bit. */
+int femfct_solidbody_adjoint_obs(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                                 const double* u_traj, const double* uhat_traj, const double* theta, double tau,
+                                 const double* window, double* p_traj, int32_t num_steps, double dt, double eps,
+                                 double rot_scale, double bx, double by, int32_t batch);
+/* the same for the sweep with the explicit reaction term: rhs_n = (theta[n]/dt) Mw (uhat_n - u_n) - Mg(g_n) p_{n+1} */
+int femfct_linear_adjoint_react_obs(femfct_ctx* ctx, const double* Aadj_ell, const double* g_traj, const double* u_traj,
+                                    const double* uhat_traj, const double* theta, double tau, const double* window,
+                                    double* p_traj, int32_t num_steps, double dt, double eps, int32_t batch);
+/* the load of one level on its own: out = (theta_dev[level]/dt) Mw (a - b); a, b, out: n doubles per batch member.
+ * theta_dev[level] == 0: out = 0, a and b are not read. */
+int femfct_obs_load(femfct_ctx* ctx, const double* a_dev, const double* b_dev, const double* theta_dev, int32_t level,
+                    double dt, const double* window_dev, double* out_dev, int32_t batch);
+/* out_host[b] = 1/2 sum_n cost_w_dev[n] (u_n - uhat_n)^T Mw (u_n - uhat_n) of batch member b (trajectories of
+ * (num_steps + 1)*n doubles); cost_w_dev: num_steps + 1 doubles on the device, levels of zero weight are not read.  The
+ * result of a member does not depend on the batch size.  Synchronises. */
+int femfct_obs_cost(femfct_ctx* ctx, const double* u_traj, const double* uhat_traj, const double* cost_w_dev,
+                    const double* window_dev, int32_t num_steps, int32_t batch, double* out_host);
 /* out_ell = assemble(f_h*u*v*dx) for the P1 function with nodal values f_dev (n doubles).  Synchronises. */
 int femfct_assemble_weighted_mass(femfct_ctx* ctx, const double* f_dev, double* out_ell);
 /* solver diagnostics of the most recent sweep: info_host[step*batch + b] */
