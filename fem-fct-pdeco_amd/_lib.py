@@ -119,6 +119,9 @@ SIGNATURES = {
     "femfct_react_load": (C.c_int, [_p, _p, _p, _p, _p, _i]),
     "femfct_solidbody_adjoint_obs": (C.c_int, [_p, _p, _p, _i, _p, _p, _p, _d, _p, _p, _i, _d, _d, _d, _d, _d, _i]),
     "femfct_linear_adjoint_react_obs": (C.c_int, [_p, _p, _p, _p, _p, _p, _d, _p, _p, _i, _d, _d, _i]),
+    "femfct_nonlinear_adjoint_obs": (C.c_int, [_p, _p, _p, _p, _p, _d, _p, _p, _i, _d, _d, _i]),
+    "femfct_schnak_adjoint_obs": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _d, _p, _d, _p, _p, _p, _i, _d, _p, _i]),
+    "femfct_chtxs_adjoint_obs": (C.c_int, [_p, _p, _p, _p, _p, _p, _d, _p, _d, _p, _p, _p, _p, _i, _d, _p, _d, _p, _i, _i]),
     "femfct_obs_load": (C.c_int, [_p, _p, _p, _p, _i, _d, _p, _p, _i]),
     "femfct_obs_cost": (C.c_int, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "femfct_assemble_weighted_mass": (C.c_int, [_p, _p, _p]),

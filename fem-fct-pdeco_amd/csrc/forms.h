@@ -56,6 +56,18 @@ struct GrowthLoadSpec {
     int64_t a_bs = 0, b_bs = 0, q1_bs = 0, q2_bs = 0, da_bs = 0, db_bs = 0;
 };
 
+// The misfit a snapshot sweep of the three PDE systems adds to a load of its adjoint step (ObsTail, forms_device.h), in the
+// launch that assembles that load:
+//   out_i += pre * (theta/dt) * (Mw(w) (a - b))_i   (mass)      or      out_i += pre * (theta/dt) * w_i (a_i - b_i)   (nodal)
+// theta: the level's weight, read on the device through the level counter; theta == 0: a and b are not read.  theta
+// absent: no term (the variable is not observed).  w absent: no window (Mw = M, w = 1); w is shared by the batch.
+struct ObsTerm {
+    VecRef theta{nullptr, nullptr, 0, 0}, a{nullptr, nullptr, 0, 0}, b{nullptr, nullptr, 0, 0}, w{nullptr, nullptr, 0, 0};
+    int64_t a_bs = 0, b_bs = 0;
+    double pre = 1.0, dt = 1.0;
+    int mass = 1;
+};
+
 // up to three independent forms of a time step in one launch (kernels_forms.hip: k_forms2 / k_forms3)
 enum { FORM_NONE = 0, FORM_WMASS, FORM_LOAD, FORM_CHTXS_MAT0, FORM_CHTXS_MAT1 };
 struct ChtxsMatSpec {
@@ -77,9 +89,12 @@ struct FormGroup {
     femfct_ctx* ctx;
     int n = 0;
     FormJob jobs[3];
+    bool has_obs = false;       // the group's load carries a snapshot misfit: the k_forms*_obs kernels
+    ObsTerm obs;
     explicit FormGroup(femfct_ctx* c) : ctx(c) {}
     void weighted_mass(const WMassSpec& sp, double* out, int32_t batch);
     void load(const LoadSpec& sp, double* out, int32_t batch);
+    void load_obs(const LoadSpec& sp, const ObsTerm& t, double* out, int32_t batch);   // the group's only load: any other load is launched in a group of its own
     void chtxs_matrix(int adjoint, VecRef u, int64_t u_bs, VecRef v, int64_t v_bs, double Dm, double chi, double eta,
                       double* out, int32_t batch);
     int launch();
@@ -98,6 +113,13 @@ int femfct_enqueue_growth_load(femfct_ctx* ctx, const GrowthLoadSpec& sp, double
 // the chemotaxis flux matrix of a step (c.p0, p1, p2 = Dm, chi, eta) and its growth load in one launch
 int femfct_enqueue_chtxs_matrix_growth(femfct_ctx* ctx, int adjoint, const ChtxsMatSpec& c, double* mat_out,
                                        const GrowthLoadSpec& sp, double* load_out, int32_t batch);
+// the same launches with a snapshot misfit in the load (k_*_obs in kernels_forms.hip, kernels_growth.hip); the forms are those of the kernels above
+int femfct_enqueue_load_obs(femfct_ctx* ctx, const LoadSpec& sp, const ObsTerm& t, double* out, int32_t batch);
+int femfct_enqueue_forms_obs(femfct_ctx* ctx, const FormJob* jobs, int cnt, const ObsTerm& t);
+int femfct_enqueue_chtxs_matrix_growth_obs(femfct_ctx* ctx, const ChtxsMatSpec& c, double* mat_out, const GrowthLoadSpec& sp,
+                                           const ObsTerm& t, double* load_out, int32_t batch);     // adjoint matrix
+int femfct_enqueue_chtxs_rhs_q_obs(femfct_ctx* ctx, VecRef u, int64_t u_bs, VecRef p, int64_t p_bs, double chi, double eta,
+                                   const ObsTerm& t, double* out, int32_t batch, VecRef mx, int64_t mx_bs, double s0, double s2);
 // mx.base != null: out = s0 * M mx + s2 * rhs_q in the same pass (the species right-hand side, helpers.py:1538)
 int femfct_enqueue_chtxs_rhs_q(femfct_ctx* ctx, VecRef u, int64_t u_bs, VecRef p, int64_t p_bs, double chi, double eta,
                                VecRef da, int64_t da_bs, VecRef db, int64_t db_bs, double* out, int32_t batch,

@@ -9,6 +9,7 @@
 #include "device_utils.h"
 #include "stencil.h"
 #include "forms.h"
+#include "obs_device.h"
 
 namespace {
 
@@ -41,6 +42,60 @@ __device__ __forceinline__ void gather7(const double* __restrict__ f, const int3
 __device__ __forceinline__ const double* bptr(const VecRef& r, int64_t bstride, int bz) {
     const double* p = vec_ptr(r);
     return p ? p + bz * bstride : nullptr;
+}
+
+// What a load form adds to its row's value before it is stored: nothing (the empty tail is inlined away: the forms' own
+// kernels keep their machine code), or the level-weighted misfit of a snapshot sweep of the three PDE systems (ObsTerm,
+// forms.h): the thread that owns row i adds it as the last term, where the all-time forms add theirs, so theta_n = dt gives
+// the all-time bits and theta_n = 0 the final-time bits.  theta is read through the device-side level counter: one captured
+// step serves every level, and at theta_n == 0 neither the target nor the state is read (uniform over the grid).
+struct NoTail {
+    __device__ __forceinline__ double operator()(int, double res) const { return res; }
+};
+
+struct ObsTail {
+    const MeshArgs& m;
+    bool on;                    // the level is observed
+    double sc;                  // pre * theta/dt
+    const double *a, *b, *w;
+    int mass;
+    __device__ __forceinline__ double operator()(int i, double res) const {
+        if (!on) return res;
+        const int n = m.n;
+        if (!mass) {
+            const double d = a[i] - b[i];
+            return res + sc * (w ? w[i] * d : d);
+        }
+        if (!w) {               // (M (a - b))_i, the expression of form_load's s3 term
+            double acc = m.M[i] * (a[i] - b[i]);
+#pragma unroll
+            for (int s = 1; s < STENCIL_W; ++s) {
+                const int64_t idx = (int64_t)s * n + i;
+                const int j = m.cols[idx];
+                acc += m.M[idx] * (a[j] - b[j]);
+            }
+            return res + sc * acc;
+        }
+        double wv[STENCIL_W], dv[STENCIL_W];
+        wv[0] = w[i]; dv[0] = a[i] - b[i];
+#pragma unroll
+        for (int s = 1; s < STENCIL_W; ++s) {
+            const int j = m.cols[(int64_t)s * n + i];
+            wv[s] = w[j]; dv[s] = a[j] - b[j];
+        }
+        const double k60 = 0.5 * m.h * m.h / 60.0;
+        double r = 0.0;
+        for_each_tri(node_xy(i, m.d2v, m.N), m.nc, [&](const TriInfo& T) { r += k60 * p1_triple_term(T, wv, dv); });
+        return res + sc * r;
+    }
+};
+
+__device__ __forceinline__ ObsTail obs_tail(const MeshArgs& m, const ObsTerm& t, int bz) {
+    const double* thp = vec_ptr(t.theta);
+    const double th = thp ? *thp : 0.0;         // the level's weight: one value for the whole grid
+    const bool on = th != 0.0;
+    return ObsTail{m, on, t.pre * (th / t.dt), on ? bptr(t.a, t.a_bs, bz) : nullptr, on ? bptr(t.b, t.b_bs, bz) : nullptr,
+                   vec_ptr(t.w), t.mass};
 }
 
 // ---------------------------------------------------------------------------

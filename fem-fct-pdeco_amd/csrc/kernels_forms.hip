@@ -67,7 +67,9 @@ __device__ __forceinline__ void form_weighted_mass(const MeshArgs& m, const WMas
 // (q3 may be absent = 1).  The raw nodal difference reproduces helpers.py:1506-1507,1533-1534; the
 // mass-weighted one is assemble((ea_h - eb_h)*w*dx) (Schnak_FCT_PDECO_alltime.py:268,278).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void form_load(const MeshArgs& m, const LoadSpec& sp, double* __restrict__ out_, int bz) {
+template <class Tail = NoTail>
+__device__ __forceinline__ void form_load(const MeshArgs& m, const LoadSpec& sp, double* __restrict__ out_, int bz,
+                                          Tail tail = Tail()) {
     const int n = m.n;
     const double* mx = bptr(sp.mx, sp.mx_bs, bz);
     const double* p1 = bptr(sp.p1, sp.p1_bs, bz);
@@ -128,7 +130,7 @@ __device__ __forceinline__ void form_load(const MeshArgs& m, const LoadSpec& sp,
             }
             res += sp.s3 * acc;
         }
-        out[i] = res;
+        out[i] = tail(i, res);
     }
 }
 
@@ -136,9 +138,11 @@ __device__ __forceinline__ void form_load(const MeshArgs& m, const LoadSpec& sp,
 //   out_i = int chi u_h exp(-eta u_h) (grad p_h . grad phi_i)  [+ (da_i - db_i)]    (6-point rule)
 // mx_ref != null: the species right-hand side in one pass, out_i = s0 * (M mx)_i + s2 * rhs_q_i (helpers.py:1538) -- the
 // expressions of k_load applied to this row's own value, so the bits of the two-launch sequence
+template <class Tail = NoTail>
 __device__ __forceinline__ void form_chtxs_rhs_q(const MeshArgs& m, VecRef u_ref, int64_t u_bs, VecRef p_ref, int64_t p_bs, double chi,
                                                  double eta, VecRef da_ref, int64_t da_bs, VecRef db_ref, int64_t db_bs,
-                                                 VecRef mx_ref, int64_t mx_bs, double s0, double s2, double* __restrict__ out_, int bz) {
+                                                 VecRef mx_ref, int64_t mx_bs, double s0, double s2, double* __restrict__ out_, int bz,
+                                                 Tail tail = Tail()) {
     const int n = m.n;
     const double* mx = bptr(mx_ref, mx_bs, bz);
     const double* u = bptr(u_ref, u_bs, bz);
@@ -169,6 +173,7 @@ __device__ __forceinline__ void form_chtxs_rhs_q(const MeshArgs& m, VecRef u_ref
             res += t * gpp;
         });
         if (da) res += da[i] - (db ? db[i] : 0.0);
+        res = tail(i, res);
         if (mx) {
             double fin = 0.0;
             if (s0 != 0.0) {
@@ -218,6 +223,34 @@ __global__ void k_chtxs_rhs_q(MeshArgs m, VecRef u_ref, int64_t u_bs, VecRef p_r
 __global__ void k_forms2(MeshArgs m, FormJob j0, FormJob j1) { run_form(m, blockIdx.z == 0 ? j0 : j1, blockIdx.y); }
 __global__ void k_forms3(MeshArgs m, FormJob j0, FormJob j1, FormJob j2) {
     run_form(m, blockIdx.z == 0 ? j0 : (blockIdx.z == 1 ? j1 : j2), blockIdx.y);
+}
+
+// the same launches with the snapshot misfit of a PDE-system sweep in the load (ObsTail, forms_device.h)
+__device__ __forceinline__ void run_form_obs(const MeshArgs& m, const FormJob& j, const ObsTerm& t, int bz) {
+    if (bz >= j.batch) return;
+    switch (j.type) {
+        case FORM_WMASS: form_weighted_mass(m, j.w, j.out, bz); break;
+        case FORM_LOAD: form_load(m, j.l, j.out, bz, obs_tail(m, t, bz)); break;
+        case FORM_CHTXS_MAT0: form_chtxs_matrix<0>(m, j.c.u, j.c.u_bs, j.c.v, j.c.v_bs, j.c.p0, j.c.p1, j.c.p2, j.out, bz); break;
+        case FORM_CHTXS_MAT1: form_chtxs_matrix<1>(m, j.c.u, j.c.u_bs, j.c.v, j.c.v_bs, j.c.p0, j.c.p1, j.c.p2, j.out, bz); break;
+        default: break;
+    }
+}
+
+__global__ void k_load_obs(MeshArgs m, LoadSpec sp, ObsTerm t, double* __restrict__ out_) {
+    form_load(m, sp, out_, blockIdx.y, obs_tail(m, t, blockIdx.y));
+}
+__global__ void k_forms2_obs(MeshArgs m, FormJob j0, FormJob j1, ObsTerm t) {
+    run_form_obs(m, blockIdx.z == 0 ? j0 : j1, t, blockIdx.y);
+}
+__global__ void k_forms3_obs(MeshArgs m, FormJob j0, FormJob j1, FormJob j2, ObsTerm t) {
+    run_form_obs(m, blockIdx.z == 0 ? j0 : (blockIdx.z == 1 ? j1 : j2), t, blockIdx.y);
+}
+__global__ void k_chtxs_rhs_q_obs(MeshArgs m, VecRef u_ref, int64_t u_bs, VecRef p_ref, int64_t p_bs, double chi, double eta,
+                                  ObsTerm t, VecRef mx_ref, int64_t mx_bs, double s0, double s2, double* __restrict__ out_) {
+    const VecRef none{nullptr, nullptr, 0, 0};
+    form_chtxs_rhs_q(m, u_ref, u_bs, p_ref, p_bs, chi, eta, none, 0, none, 0, mx_ref, mx_bs, s0, s2, out_, blockIdx.y,
+                     obs_tail(m, t, blockIdx.y));
 }
 
 }  // namespace
@@ -270,6 +303,50 @@ int femfct_enqueue_chtxs_rhs_q(femfct_ctx* ctx, VecRef u, int64_t u_bs, VecRef p
     return FEMFCT_OK;
 }
 
+int femfct_enqueue_load_obs(femfct_ctx* ctx, const LoadSpec& sp, const ObsTerm& t, double* out, int32_t batch) {
+    LaunchGeom g = femfct_geom(ctx, batch);
+    femfct_prof_begin(ctx, KC_ASSEMBLE);
+    hipLaunchKernelGGL(k_load_obs, g.grid, g.block, 0, ctx->stream, femfct_mesh_args(ctx), sp, t, out);
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
+int femfct_enqueue_forms_obs(femfct_ctx* ctx, const FormJob* jobs, int cnt, const ObsTerm& t) {
+    if (cnt == 1 || !ctx->form_groups) {          // one form, or FEMFCT_FORM_GROUPS=0: every form in its own launch, in order
+        for (int k = 0; k < cnt; ++k) {
+            const FormJob& j = jobs[k];
+            int r = FEMFCT_OK;
+            if (j.type == FORM_WMASS) r = femfct_enqueue_weighted_mass(ctx, j.w, j.out, j.batch);
+            else if (j.type == FORM_LOAD) r = femfct_enqueue_load_obs(ctx, j.l, t, j.out, j.batch);
+            else r = femfct_enqueue_chtxs_matrix(ctx, j.type == FORM_CHTXS_MAT1, j.c.u, j.c.u_bs, j.c.v, j.c.v_bs, j.c.p0, j.c.p1,
+                                                 j.c.p2, j.out, j.batch);
+            if (r != FEMFCT_OK) return r;
+        }
+        return FEMFCT_OK;
+    }
+    int32_t bmax = 1;
+    for (int k = 0; k < cnt; ++k) bmax = std::max(bmax, jobs[k].batch);
+    LaunchGeom g = femfct_geom(ctx, bmax);
+    g.grid.z = cnt;
+    femfct_prof_begin(ctx, KC_ASSEMBLE);
+    if (cnt == 2) hipLaunchKernelGGL(k_forms2_obs, g.grid, g.block, 0, ctx->stream, femfct_mesh_args(ctx), jobs[0], jobs[1], t);
+    else hipLaunchKernelGGL(k_forms3_obs, g.grid, g.block, 0, ctx->stream, femfct_mesh_args(ctx), jobs[0], jobs[1], jobs[2], t);
+    femfct_prof_end(ctx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return femfct_fail(ctx, FEMFCT_ERR_HIP, "form group launch failed: %s", hipGetErrorString(e));
+    return FEMFCT_OK;
+}
+
+int femfct_enqueue_chtxs_rhs_q_obs(femfct_ctx* ctx, VecRef u, int64_t u_bs, VecRef p, int64_t p_bs, double chi, double eta,
+                                   const ObsTerm& t, double* out, int32_t batch, VecRef mx, int64_t mx_bs, double s0, double s2) {
+    LaunchGeom g = femfct_geom(ctx, batch);
+    femfct_prof_begin(ctx, KC_ASSEMBLE);
+    hipLaunchKernelGGL(k_chtxs_rhs_q_obs, g.grid, g.block, 0, ctx->stream, femfct_mesh_args(ctx), u, u_bs, p, p_bs, chi, eta, t,
+                       mx, mx_bs, s0, s2, out);
+    femfct_prof_end(ctx);
+    return FEMFCT_OK;
+}
+
 // ------------------------------------------------------------------ FormGroup
 void FormGroup::weighted_mass(const WMassSpec& sp, double* out, int32_t batch) {
     if (n == 3) launch();
@@ -279,10 +356,17 @@ void FormGroup::weighted_mass(const WMassSpec& sp, double* out, int32_t batch) {
 }
 
 void FormGroup::load(const LoadSpec& sp, double* out, int32_t batch) {
-    if (n == 3) launch();
+    if (n == 3 || has_obs) launch();          // (the misfit of a group goes to its one load: another load starts a new group)
     FormJob& j = jobs[n++];
     j = FormJob{};
     j.type = FORM_LOAD; j.batch = batch; j.out = out; j.l = sp;
+}
+
+void FormGroup::load_obs(const LoadSpec& sp, const ObsTerm& t, double* out, int32_t batch) {
+    for (int k = 0; k < n; ++k)
+        if (jobs[k].type == FORM_LOAD) { launch(); break; }     // a load collected before must not get this misfit
+    load(sp, out, batch);
+    has_obs = true; obs = t;
 }
 
 void FormGroup::chtxs_matrix(int adjoint, VecRef u, int64_t u_bs, VecRef v, int64_t v_bs, double Dm, double chi, double eta,
@@ -298,6 +382,10 @@ int FormGroup::launch() {
     const int cnt = n;
     n = 0;
     if (cnt == 0) return FEMFCT_OK;
+    if (has_obs) {
+        has_obs = false;
+        return femfct_enqueue_forms_obs(ctx, jobs, cnt, obs);
+    }
     if (cnt == 1 || !ctx->form_groups) {          // one form, or FEMFCT_FORM_GROUPS=0: the forms' own kernels, in order
         for (int k = 0; k < cnt; ++k) {
             const FormJob& j = jobs[k];

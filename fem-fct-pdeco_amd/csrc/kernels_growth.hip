@@ -19,7 +19,9 @@
 
 namespace {
 
-__device__ __forceinline__ void form_growth_load(const MeshArgs& m, const GrowthLoadSpec& sp, double* __restrict__ out_, int bz) {
+template <class Tail = NoTail>
+__device__ __forceinline__ void form_growth_load(const MeshArgs& m, const GrowthLoadSpec& sp, double* __restrict__ out_, int bz,
+                                                 Tail tail = Tail()) {
     const int n = m.n;
     const double* a = bptr(sp.a, sp.a_bs, bz);
     const double* b = bptr(sp.b, sp.b_bs, bz);       // may be absent: 1
@@ -55,7 +57,7 @@ __device__ __forceinline__ void form_growth_load(const MeshArgs& m, const Growth
         double res = gr;
         if (q1) res += sp.s1 * ld;
         if (da) res += sp.s2 * (da[i] - (db ? db[i] : 0.0));
-        out[i] = res;
+        out[i] = tail(i, res);
     }
 }
 
@@ -66,6 +68,16 @@ __global__ void k_chtxs_matrix_growth(MeshArgs m, ChtxsMatSpec c, double* __rest
                                       double* __restrict__ load_out) {
     if (blockIdx.z == 0) form_chtxs_matrix<ADJ>(m, c.u, c.u_bs, c.v, c.v_bs, c.p0, c.p1, c.p2, mat_out, blockIdx.y);
     else form_growth_load(m, sp, load_out, blockIdx.y);
+}
+
+// the adjoint launch with the snapshot misfit of the cell density in the load (ObsTail, forms_device.h)
+// z0 = 0, gridDim.z = 2: the adjoint flux matrix and the load; z0 = 1, gridDim.z = 1: the load alone
+// (blocks of 64 or 256 threads, femfct_geom: with the bound the growth load and the windowed misfit fit the register file;
+// without it the compiler assumes 1024 threads, 128 VGPRs, and spills 15 of them)
+__global__ void __launch_bounds__(256) k_chtxs_matrix_growth_obs(MeshArgs m, ChtxsMatSpec c, double* __restrict__ mat_out, GrowthLoadSpec sp, ObsTerm t,
+                                          double* __restrict__ load_out, int z0) {
+    if (blockIdx.z + z0 == 0) form_chtxs_matrix<1>(m, c.u, c.u_bs, c.v, c.v_bs, c.p0, c.p1, c.p2, mat_out, blockIdx.y);
+    else form_growth_load(m, sp, load_out, blockIdx.y, obs_tail(m, t, blockIdx.y));
 }
 
 }  // namespace
@@ -92,6 +104,26 @@ int femfct_enqueue_chtxs_matrix_growth(femfct_ctx* ctx, int adjoint, const Chtxs
         hipLaunchKernelGGL(k_chtxs_matrix_growth<1>, g.grid, g.block, 0, ctx->stream, femfct_mesh_args(ctx), c, mat_out, sp, load_out);
     else
         hipLaunchKernelGGL(k_chtxs_matrix_growth<0>, g.grid, g.block, 0, ctx->stream, femfct_mesh_args(ctx), c, mat_out, sp, load_out);
+    femfct_prof_end(ctx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return femfct_fail(ctx, FEMFCT_ERR_HIP, "growth form launch failed: %s", hipGetErrorString(e));
+    return FEMFCT_OK;
+}
+
+int femfct_enqueue_chtxs_matrix_growth_obs(femfct_ctx* ctx, const ChtxsMatSpec& c, double* mat_out, const GrowthLoadSpec& sp,
+                                           const ObsTerm& t, double* load_out, int32_t batch) {
+    LaunchGeom g = femfct_geom(ctx, batch);
+    int z0 = 0;
+    if (!ctx->form_groups) {      // FEMFCT_FORM_GROUPS=0: the matrix in its own launch, then the load alone -- the same bits
+        int r = femfct_enqueue_chtxs_matrix(ctx, 1, c.u, c.u_bs, c.v, c.v_bs, c.p0, c.p1, c.p2, mat_out, batch);
+        if (r != FEMFCT_OK) return r;
+        z0 = 1;
+    } else {
+        g.grid.z = 2;
+    }
+    femfct_prof_begin(ctx, KC_ASSEMBLE);
+    hipLaunchKernelGGL(k_chtxs_matrix_growth_obs, g.grid, g.block, 0, ctx->stream, femfct_mesh_args(ctx), c, mat_out, sp, t,
+                       load_out, z0);
     femfct_prof_end(ctx);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return femfct_fail(ctx, FEMFCT_ERR_HIP, "growth form launch failed: %s", hipGetErrorString(e));

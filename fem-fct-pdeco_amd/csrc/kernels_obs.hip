@@ -21,6 +21,7 @@
 #include "stencil.h"
 #include "forms.h"
 #include "solidbody_op.h"
+#include "obs_device.h"
 
 #include <algorithm>
 
@@ -35,10 +36,7 @@ __device__ __forceinline__ const double* member(const VecRef& r, int64_t bstride
 __device__ __forceinline__ double weighted_mass_row(const NodeXY& P, int nc, double k60, const double* fv, const double* xv) {
     double r = 0.0;
     for_each_tri(P, nc, [&](const TriInfo& T, int, int) {
-        const int sq = T.slot[(T.pl + 1) % 3], sr = T.slot[(T.pl + 2) % 3];
-        const double fp = fv[0], fq = fv[sq], fr = fv[sr];
-        const double t = xv[0] * (6.0 * fp + 2.0 * fq + 2.0 * fr) + xv[sq] * (2.0 * fp + 2.0 * fq + fr) +
-                         xv[sr] * (2.0 * fp + fq + 2.0 * fr);
+        const double t = p1_triple_term(T, fv, xv);
         r += k60 * t;
     });
     return r;

@@ -112,6 +112,54 @@ int parse_growth(femfct_ctx* ctx, const double* growth, Growth* g) {
     return FEMFCT_OK;
 }
 
+// Snapshot observations of a sweep's two state variables (ObsTail, forms_device.h): theta (num_steps + 1 device doubles, read per
+// level through the level counter; null: the variable is not observed and its target may be null), tau (weight of the terminal
+// condition), one window (null: none) for both, and the load: mass (Mw (hat - state), the discrete adjoint of the cost) or
+// nodal (w .* (hat - state), as helpers.py:1506-1507,1533-1534 load it).  Graph keys: a sweep with observations carries its
+// own tag (kind + 400: next to the per-step + 100 and the growth + 200) and these words; the sweep kind (budgets, full rows)
+// is that of the system's adjoint sweep, the operators being the same.
+struct SysObs {
+    const double *theta_u, *theta_v;
+    double tau_u, tau_v;
+    const double* window;
+    int32_t mass;
+    static uint64_t tag(const SysObs* o, uint64_t t) { return o ? t + 400 : t; }
+    static void key_tail(const SysObs* o, femfct_ctx::GraphKey& k) {
+        if (!o) return;
+        k.push_back(key_bits(o->theta_u)); k.push_back(key_bits(o->theta_v)); k.push_back(key_bits(o->window));
+        k.push_back(key_bits(o->mass));         // (tau enters the terminal condition alone, outside the captured step)
+    }
+    // the misfit of the step being enqueued: pre * (theta_n/dt) * [Mw | w .*] (hat_n - state_n)
+    ObsTerm term(const femfct_ctx* ctx, const Lv& L, const double* theta, const double* hat, const double* state, int64_t ts,
+                 double pre, double dt) const {
+        ObsTerm t;
+        if (!theta) return t;
+        t.theta = lref(ctx, theta, L.lv, 1, 0);
+        t.a = L(hat, 0); t.a_bs = ts; t.b = L(state, 0); t.b_bs = ts;
+        t.w = make_ref(window); t.pre = pre; t.dt = dt; t.mass = mass;
+        return t;
+    }
+};
+
+int check_obs(femfct_ctx* ctx, const SysObs& o, const double* uhat, const double* vhat) {
+    ARG_TRY(ctx, std::isfinite(o.tau_u) && std::isfinite(o.tau_v), "tau must be finite");
+    ARG_TRY(ctx, o.mass == FEMFCT_MISFIT_NODAL || o.mass == FEMFCT_MISFIT_MASS, "unknown misfit load");
+    ARG_TRY(ctx, (uhat || !o.theta_u) && (vhat || !o.theta_v), "an observed variable needs its target trajectory");
+    return FEMFCT_OK;
+}
+
+// terminal condition of a sweep with observations: adj_Nt = tau * omega .* (hat_Nt - state_Nt), zeros for tau == 0 or a
+// variable that is not observed (the target's terminal level is not read then)
+int obs_terminal(femfct_ctx* ctx, const double* theta, double tau, const double* window, const double* hat,
+                 const double* state, double* adj, int32_t num_steps, int32_t batch) {
+    const int64_t n = ctx->n, ts = (int64_t)(num_steps + 1) * n, off = (int64_t)num_steps * n;
+    if (!theta || tau == 0.0) {
+        for (int32_t b = 0; b < batch; ++b) HIP_TRY(ctx, hipMemsetAsync(adj + b * ts + off, 0, sizeof(double) * n, ctx->stream));
+        return FEMFCT_OK;
+    }
+    return femfct_enqueue_obs_terminal(ctx, tau, window, hat + off, ts, state + off, ts, adj + off, ts, batch);
+}
+
 int check_common(femfct_ctx* ctx, int32_t num_steps, double dt, int32_t batch) {
     ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
     ARG_TRY(ctx, num_steps >= 1 && dt > 0 && batch >= 1, "need num_steps >= 1, dt > 0, batch >= 1");
@@ -282,10 +330,11 @@ int femfct_nonlinear_forward_ct(femfct_ctx* ctx, const double* Aw_ell, const dou
 // budgets leave those of the final-time sweep as they were.  Both launch the same kernels per step.
 static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat,
                              int32_t uhat_shared, bool alltime, double* p_traj, int32_t num_steps, double dt, double eps,
-                             int32_t batch) {
+                             int32_t batch, const SysObs* obs = nullptr) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
-    ARG_TRY(ctx, Aw_ell && u_traj && uhat && p_traj, "null argument");
+    ARG_TRY(ctx, Aw_ell && u_traj && (uhat || obs) && p_traj, "null argument");
+    if (obs && (rc = check_obs(ctx, *obs, uhat, nullptr)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     const int64_t n = ctx->n, wn = (int64_t)ctx->W * n, ts = (int64_t)(num_steps + 1) * n;
     const SweepKind kind = alltime ? SWEEP_NONLINEAR_ADJOINT_ALLTIME : SWEEP_NONLINEAR_ADJOINT;
@@ -293,6 +342,7 @@ static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double
     Lv L{ctx, ctx->d_level, n};
     auto begin = [&]() {
         for (int32_t b = 0; b < batch; ++b) femfct_enqueue_axpby(ctx, wn, eps, ctx->d_Ad, 1.0, Aw_ell, ctx->d_trA + b * wn);
+        if (obs) return obs_terminal(ctx, obs->theta_u, obs->tau_u, obs->window, uhat, u_traj, p_traj, num_steps, batch);
         if (alltime) {      // pk = np.zeros(vec_length) (nonlinear_FCT_PDECO_alltime.py:200)
             for (int32_t b = 0; b < batch; ++b)
                 HIP_TRY(ctx, hipMemsetAsync(p_traj + b * ts + (int64_t)num_steps * n, 0, sizeof(double) * n, ctx->stream));
@@ -301,10 +351,11 @@ static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double
         return terminal_diff(ctx, uhat, u_traj, p_traj, num_steps, batch);
     };
     auto step = [&](int budget, int, int reps) {
-        auto key = KEY((uint64_t)kind, key_bits(Aw_ell), key_bits(u_traj), key_bits(uhat), key_bits(p_traj),
+        auto key = KEY(SysObs::tag(obs, (uint64_t)kind), key_bits(Aw_ell), key_bits(u_traj), key_bits(uhat), key_bits(p_traj),
                        key_bits(num_steps), key_bits(dt), key_bits(eps), key_bits(batch), key_bits((int32_t)budget),
                        key_bits(ctx->rel_tol));
         if (alltime) key.push_back(key_bits(shared));
+        SysObs::key_tail(obs, key);
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             WMassSpec ws;  // Mat_rhs = M_u2(u_n) - M (helpers.py:1032-1034)
             ws.alpha = -1.0; ws.beta = 1.0; ws.f1 = L(u_traj, 0); ws.f2 = L(u_traj, 0); ws.f1_bs = ws.f2_bs = ts;
@@ -312,10 +363,12 @@ static int nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double
             int64_t rhs_bs = 0;
             if (alltime) {          // assemble((uhat_n - u_n)*v*dx) (:209-210) rides in the weighted mass's launch
                 LoadSpec lp;
-                lp.s3 = 1.0; lp.ea = L(uhat, 0); lp.ea_bs = shared ? 0 : ts; lp.eb = L(u_traj, 0); lp.eb_bs = ts;
+                if (!obs) { lp.s3 = 1.0; lp.ea = L(uhat, 0); lp.ea_bs = shared ? 0 : ts; lp.eb = L(u_traj, 0); lp.eb_bs = ts; }
                 FormGroup fg(ctx);
                 fg.weighted_mass(ws, ctx->d_trN, batch);
-                fg.load(lp, ctx->d_trRhs, batch);
+                // observations: rhs = (theta_n/dt) Mw (uhat_n - u_n), theta_n read on the device, in the same launch
+                if (obs) fg.load_obs(lp, obs->term(ctx, L, obs->theta_u, uhat, u_traj, ts, 1.0, dt), ctx->d_trRhs, batch);
+                else fg.load(lp, ctx->d_trRhs, batch);
                 int r = fg.launch();
                 if (r != FEMFCT_OK) return r;
                 rhs = make_ref(ctx->d_trRhs);
@@ -338,6 +391,15 @@ int femfct_nonlinear_adjoint(femfct_ctx* ctx, const double* Aw_ell, const double
                              double* p_traj, int32_t num_steps, double dt, double eps, int32_t batch) {
     FEMFCT_ENTER(ctx);
     return nonlinear_adjoint(ctx, Aw_ell, u_traj, uhat_T, 0, false, p_traj, num_steps, dt, eps, batch);
+}
+
+// snapshot observations (SysObs): the all-time sweep's kind and launches, uhat_traj a trajectory per member
+int femfct_nonlinear_adjoint_obs(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat_traj,
+                                 const double* theta_u_dev, double tau_u, const double* window_dev, double* p_traj,
+                                 int32_t num_steps, double dt, double eps, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    const SysObs obs{theta_u_dev, nullptr, tau_u, 0.0, window_dev, FEMFCT_MISFIT_MASS};
+    return nonlinear_adjoint(ctx, Aw_ell, u_traj, uhat_traj, 0, true, p_traj, num_steps, dt, eps, batch, &obs);
 }
 
 int femfct_nonlinear_adjoint_alltime(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat_traj,
@@ -461,14 +523,39 @@ int femfct_schnak_adjoint(femfct_ctx* ctx, const double* AwT_ell, const double* 
 
 // with the separable time-dependent wind of femfct_schnak_forward_tw: the step that produces level n uses s(t_n)
 // (helpers.py:664-679: t -= dt; wind.t = t)
+static int schnak_adjoint(femfct_ctx* ctx, const double* AwT_ell, const double* wind_scale_host, const double* u_traj,
+                          const double* v_traj, const double* uhat_T, const double* vhat_T, double* p_traj, double* q_traj,
+                          int32_t num_steps, double dt, const double* par, int32_t alltime, int32_t batch, const SysObs* obs);
+
 int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const double* wind_scale_host, const double* u_traj,
                              const double* v_traj, const double* uhat_T, const double* vhat_T, double* p_traj,
                              double* q_traj, int32_t num_steps, double dt, const double* par, int32_t alltime,
                              int32_t batch) {
     FEMFCT_ENTER(ctx);
+    return schnak_adjoint(ctx, AwT_ell, wind_scale_host, u_traj, v_traj, uhat_T, vhat_T, p_traj, q_traj, num_steps, dt, par,
+                          alltime, batch, nullptr);
+}
+
+// snapshot observations (SysObs): uhat/vhat are trajectories; the q right-hand side gains dt*(theta^v_n/dt) Mw (vhat_n - v_n)
+// and the p right-hand side (theta^u_n/dt) Mw (uhat_n - u_n), in the launches that carry the all-time misfits
+int femfct_schnak_adjoint_obs(femfct_ctx* ctx, const double* AwT_ell, const double* wind_scale_host, const double* u_traj,
+                              const double* v_traj, const double* uhat_traj, const double* vhat_traj,
+                              const double* theta_u_dev, double tau_u, const double* theta_v_dev, double tau_v,
+                              const double* window_dev, double* p_traj, double* q_traj, int32_t num_steps, double dt,
+                              const double* par, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    const SysObs obs{theta_u_dev, theta_v_dev, tau_u, tau_v, window_dev, FEMFCT_MISFIT_MASS};
+    return schnak_adjoint(ctx, AwT_ell, wind_scale_host, u_traj, v_traj, uhat_traj, vhat_traj, p_traj, q_traj, num_steps, dt,
+                          par, 0, batch, &obs);
+}
+
+static int schnak_adjoint(femfct_ctx* ctx, const double* AwT_ell, const double* wind_scale_host, const double* u_traj,
+                          const double* v_traj, const double* uhat_T, const double* vhat_T, double* p_traj, double* q_traj,
+                          int32_t num_steps, double dt, const double* par, int32_t alltime, int32_t batch, const SysObs* obs) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
-    ARG_TRY(ctx, AwT_ell && u_traj && v_traj && uhat_T && vhat_T && p_traj && q_traj && par, "null argument");
+    ARG_TRY(ctx, AwT_ell && u_traj && v_traj && ((uhat_T && vhat_T) || obs) && p_traj && q_traj && par, "null argument");
+    if (obs && (rc = check_obs(ctx, *obs, uhat_T, vhat_T)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_krylov_ws(ctx, batch)) != FEMFCT_OK) return rc;
     const double Du = par[0], Dv = par[1], gam = par[3], om1 = par[4], om2 = par[5];
@@ -489,6 +576,11 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
     };
     auto begin = [&]() {
         if (!wsc) { int rw = wind_ops(0); if (rw != FEMFCT_OK) return rw; }
+        if (obs) {
+            int ro = obs_terminal(ctx, obs->theta_u, obs->tau_u, obs->window, uhat_T, u_traj, p_traj, num_steps, batch);
+            if (ro != FEMFCT_OK) return ro;
+            return obs_terminal(ctx, obs->theta_v, obs->tau_v, obs->window, vhat_T, v_traj, q_traj, num_steps, batch);
+        }
         if (alltime) {
             for (int32_t b = 0; b < batch; ++b) {
                 HIP_TRY(ctx, hipMemsetAsync(p_traj + b * ts + (int64_t)num_steps * n, 0, sizeof(double) * n, ctx->stream));
@@ -501,11 +593,12 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
         return terminal_diff(ctx, vhat_T, v_traj, q_traj, num_steps, batch);
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY((uint64_t)SWEEP_SCHNAK_ADJOINT, key_bits(AwT_ell), key_bits(u_traj), key_bits(v_traj), key_bits(uhat_T),
+        auto key = KEY(SysObs::tag(obs, (uint64_t)SWEEP_SCHNAK_ADJOINT), key_bits(AwT_ell), key_bits(u_traj), key_bits(v_traj), key_bits(uhat_T),
                        key_bits(vhat_T), key_bits(p_traj), key_bits(q_traj), key_bits(num_steps), key_bits(dt),
                        key_bits(Du), key_bits(Dv), key_bits(gam), key_bits(om1), key_bits(om2), key_bits(batch),
                        key_bits(alltime), key_bits((int32_t)budget), key_bits((int32_t)kbudget), key_bits(ctx->rel_tol), key_bits(ctx->kry_tol),
                        key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_SCHNAK_ADJOINT)), key_bits(wsc));
+        SysObs::key_tail(obs, key);
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             if (wsc) wind_ops(0);       // level counter = n: wind.t = t_n (helpers.py:664,679)
             // q first (helpers.py:683-686): Mat_q = M + dt*(Dv*Ad - omega2*A' + gamma*M_u2(u_n))
@@ -521,7 +614,8 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
             wn_.alpha = gam; wn_.beta = -2.0 * gam; wn_.f1 = L(u_traj, 0); wn_.f2 = L(v_traj, 0); wn_.f1_bs = wn_.f2_bs = ts;
             FormGroup fg(ctx);
             fg.weighted_mass(wq, ctx->d_trMat, batch);
-            fg.load(lq, ctx->d_trRhs2, batch);
+            if (obs) fg.load_obs(lq, obs->term(ctx, L, obs->theta_v, vhat_T, v_traj, ts, dt, dt), ctx->d_trRhs2, batch);
+            else fg.load(lq, ctx->d_trRhs2, batch);
             fg.weighted_mass(wn_, ctx->d_trN, batch);
             int r = fg.launch();
             if (r != FEMFCT_OK) return r;
@@ -532,7 +626,9 @@ int femfct_schnak_adjoint_tw(femfct_ctx* ctx, const double* AwT_ell, const doubl
             lp.s1 = 1.0; lp.k2 = -2.0 * gam; lp.q1 = L(u_traj, 0); lp.q2 = L(v_traj, 0); lp.q3 = L(q_traj, 0);
             lp.q1_bs = lp.q2_bs = lp.q3_bs = ts;
             if (alltime) { lp.s3 = 1.0; lp.ea = L(uhat_T, 0); lp.eb = L(u_traj, 0); lp.ea_bs = lp.eb_bs = ts; }
-            femfct_enqueue_load(ctx, lp, ctx->d_trRhs, batch);
+            if (obs) r = femfct_enqueue_load_obs(ctx, lp, obs->term(ctx, L, obs->theta_u, uhat_T, u_traj, ts, 1.0, dt), ctx->d_trRhs, batch);
+            else r = femfct_enqueue_load(ctx, lp, ctx->d_trRhs, batch);
+            if (r != FEMFCT_OK) return r;
             femfct_request_fused_end(ctx, -1, true);
             r = femfct_enqueue_step_ref(ctx, ctx->d_trA, ctx->d_trN, 0, make_ref(ctx->d_trRhs), n, L(p_traj, 1), ts, dt,
                                         L(p_traj, 0), ts, batch, budget);
@@ -636,12 +732,13 @@ int femfct_chtxs_forward_g(femfct_ctx* ctx, const double* c, int32_t c_per_step,
 static int chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat,
                          const double* vhat, double* p_traj, double* q_traj, const double* c_traj, int32_t num_steps,
                          double dt, const double* par, double rescaling, int32_t alltime, const double* growth,
-                         int32_t batch) {
+                         int32_t batch, const SysObs* obs = nullptr) {
     int rc = check_common(ctx, num_steps, dt, batch);
     if (rc != FEMFCT_OK) return rc;
     Growth gw;
     if ((rc = parse_growth(ctx, growth, &gw)) != FEMFCT_OK) return rc;
-    ARG_TRY(ctx, u_traj && v_traj && uhat && vhat && p_traj && q_traj && c_traj && par && rescaling != 0.0, "bad argument");
+    ARG_TRY(ctx, u_traj && v_traj && ((uhat && vhat) || obs) && p_traj && q_traj && c_traj && par && rescaling != 0.0, "bad argument");
+    if (obs && (rc = check_obs(ctx, *obs, uhat, vhat)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_traj_ws(ctx, batch, num_steps)) != FEMFCT_OK) return rc;
     if ((rc = femfct_ensure_krylov_ws(ctx, batch)) != FEMFCT_OK) return rc;
     const double delta = par[0], Dm = par[1], Df = par[2], chi = par[3], eta = par[4];
@@ -651,6 +748,11 @@ static int chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
         WMassSpec ws;  // Mat_q = M + dt*(Df*Ad + delta*M)  (helpers.py:1536)
         ws.alpha = 1.0 + dt * delta; ws.gamma = dt * Df; ws.base = ctx->d_Ad;
         femfct_enqueue_weighted_mass(ctx, ws, ctx->d_trBase, 1);
+        if (obs) {
+            int ro = obs_terminal(ctx, obs->theta_u, obs->tau_u, obs->window, uhat, u_traj, p_traj, num_steps, batch);
+            if (ro != FEMFCT_OK) return ro;
+            return obs_terminal(ctx, obs->theta_v, obs->tau_v, obs->window, vhat, v_traj, q_traj, num_steps, batch);
+        }
         if (!alltime) {
             terminal_diff(ctx, uhat, u_traj, p_traj, num_steps, batch);
             terminal_diff(ctx, vhat, v_traj, q_traj, num_steps, batch);
@@ -658,17 +760,24 @@ static int chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
         return FEMFCT_OK;
     };
     auto step = [&](int budget, int kbudget, int reps) {
-        auto key = KEY(gw.tag((uint64_t)SWEEP_CHTXS_ADJOINT), key_bits(u_traj), key_bits(v_traj), key_bits(uhat), key_bits(vhat), key_bits(p_traj),
+        auto key = KEY(SysObs::tag(obs, gw.tag((uint64_t)SWEEP_CHTXS_ADJOINT)), key_bits(u_traj), key_bits(v_traj), key_bits(uhat), key_bits(vhat), key_bits(p_traj),
                        key_bits(q_traj), key_bits(c_traj), key_bits(num_steps), key_bits(dt), key_bits(delta),
                        key_bits(Dm), key_bits(Df), key_bits(chi), key_bits(eta), key_bits(rescaling), key_bits(alltime),
                        key_bits(batch), key_bits((int32_t)budget), key_bits((int32_t)kbudget), key_bits(ctx->rel_tol),
                        key_bits(ctx->kry_tol), key_bits((int32_t)femfct_species_cheb(ctx, SWEEP_CHTXS_ADJOINT)));
         gw.key_tail(key);
+        SysObs::key_tail(obs, key);
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             // Mat_p = Dm*Ad - chi*Aa'(u_n, v_n)  (helpers.py:1499-1503)
             LoadSpec lp;  // assemble(c_n*q_{n+1}/r*w*dx) [+ uhat_n - u_n]  (helpers.py:1505-1507)
             lp.s1 = 1.0 / rescaling; lp.k2 = 1.0; lp.q1 = L(c_traj, 0); lp.q2 = L(q_traj, 1); lp.q1_bs = lp.q2_bs = ts;
             if (alltime) { lp.s2 = 1.0; lp.da = L(uhat, 0); lp.db = L(u_traj, 0); lp.da_bs = lp.db_bs = ts; }
+            // observations: the misfits (theta_n/dt) [Mw | omega .*] (hat_n - state_n) ride in the same two launches
+            ObsTerm tu, tv;
+            if (obs) {
+                tu = obs->term(ctx, L, obs->theta_u, uhat, u_traj, ts, 1.0, dt);
+                tv = obs->term(ctx, L, obs->theta_v, vhat, v_traj, ts, 1.0, dt);
+            }
             int r;
             if (gw.on) {            // the same load + assemble(r'(u_n)*p_{n+1}*w*dx), in the load's place
                 ChtxsMatSpec cm;
@@ -678,11 +787,13 @@ static int chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
                 gl.a = L(u_traj, 0); gl.b = L(p_traj, 1); gl.a_bs = gl.b_bs = ts;
                 gl.s1 = lp.s1 * lp.k2; gl.q1 = lp.q1; gl.q2 = lp.q2; gl.q1_bs = lp.q1_bs; gl.q2_bs = lp.q2_bs;
                 gl.s2 = lp.s2; gl.da = lp.da; gl.db = lp.db; gl.da_bs = lp.da_bs; gl.db_bs = lp.db_bs;
-                r = femfct_enqueue_chtxs_matrix_growth(ctx, 1, cm, ctx->d_trA, gl, ctx->d_trRhs, batch);
+                if (obs) r = femfct_enqueue_chtxs_matrix_growth_obs(ctx, cm, ctx->d_trA, gl, tu, ctx->d_trRhs, batch);
+                else r = femfct_enqueue_chtxs_matrix_growth(ctx, 1, cm, ctx->d_trA, gl, ctx->d_trRhs, batch);
             } else {
                 FormGroup fg(ctx);
                 fg.chtxs_matrix(1, L(u_traj, 0), ts, L(v_traj, 0), ts, Dm, chi, eta, ctx->d_trA, batch);
-                fg.load(lp, ctx->d_trRhs, batch);
+                if (obs) fg.load_obs(lp, tu, ctx->d_trRhs, batch);
+                else fg.load(lp, ctx->d_trRhs, batch);
                 r = fg.launch();
             }
             if (r != FEMFCT_OK) return r;
@@ -692,8 +803,13 @@ static int chtxs_adjoint(femfct_ctx* ctx, const double* u_traj, const double* v_
             // rhs_q = assemble(chi*u_n*exp(-eta*u_n)*dot(grad(p_n),grad(w))*dx) [+ vhat_n - v_n]  (helpers.py:1531-1534)
             VecRef none = make_ref(nullptr);
             // ... and M@q_{n+1} + dt*rhs_q (helpers.py:1538) in the same pass
-            femfct_enqueue_chtxs_rhs_q(ctx, L(u_traj, 0), ts, L(p_traj, 0), ts, chi, eta, alltime ? L(vhat, 0) : none, ts,
-                                       alltime ? L(v_traj, 0) : none, ts, ctx->d_trRhs2, batch, L(q_traj, 1), ts, 1.0, dt);
+            if (obs)
+                r = femfct_enqueue_chtxs_rhs_q_obs(ctx, L(u_traj, 0), ts, L(p_traj, 0), ts, chi, eta, tv, ctx->d_trRhs2, batch,
+                                                   L(q_traj, 1), ts, 1.0, dt);
+            else
+                r = femfct_enqueue_chtxs_rhs_q(ctx, L(u_traj, 0), ts, L(p_traj, 0), ts, chi, eta, alltime ? L(vhat, 0) : none, ts,
+                                               alltime ? L(v_traj, 0) : none, ts, ctx->d_trRhs2, batch, L(q_traj, 1), ts, 1.0, dt);
+            if (r != FEMFCT_OK) return r;
             femfct_request_fused_end(ctx, -1, true);
             r = femfct_enqueue_species_solve(ctx, SWEEP_CHTXS_ADJOINT, ctx->d_trBase, 1, ctx->d_trRhs2, L(q_traj, 1), ts, L(q_traj, 0), ts, batch, kbudget, dt * Df);
             if (r != FEMFCT_OK) return r;
@@ -719,6 +835,20 @@ int femfct_chtxs_adjoint_g(femfct_ctx* ctx, const double* u_traj, const double* 
     FEMFCT_ENTER(ctx);
     return chtxs_adjoint(ctx, u_traj, v_traj, uhat, vhat, p_traj, q_traj, c_traj, num_steps, dt, par, rescaling, alltime,
                          growth, batch);
+}
+
+// snapshot observations (SysObs) with either load: misfit = FEMFCT_MISFIT_NODAL keeps the reference's raw nodal misfits
+// (its all-time corner is femfct_chtxs_adjoint[_g] with alltime = 1 and zero terminal levels), FEMFCT_MISFIT_MASS loads
+// Mw (hat_n - state_n), the discrete adjoint of the tracking cost
+int femfct_chtxs_adjoint_obs(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat_traj,
+                             const double* vhat_traj, const double* theta_u_dev, double tau_u, const double* theta_v_dev,
+                             double tau_v, const double* window_dev, double* p_traj, double* q_traj, const double* c_traj,
+                             int32_t num_steps, double dt, const double* par, double rescaling, const double* growth,
+                             int32_t misfit, int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    const SysObs obs{theta_u_dev, theta_v_dev, tau_u, tau_v, window_dev, misfit};
+    return chtxs_adjoint(ctx, u_traj, v_traj, uhat_traj, vhat_traj, p_traj, q_traj, c_traj, num_steps, dt, par, rescaling, 0,
+                         growth, batch, &obs);
 }
 
 // BiCGStab diagnostics of the most recent sweep that used it: info_host[step*batch + b]

@@ -83,6 +83,24 @@ def _growth(growth) -> np.ndarray:
     return g
 
 
+MISFITS = {"nodal": 0, "mass": 1}
+
+
+class DeviceObs:
+    """Snapshot observations of the state variables of a PDE-system sweep, on the device: ``theta_u`` / ``theta_v``
+    (num_steps + 1 doubles; None: the variable is not observed and its target may be None), the terminal weights
+    ``tau_u`` / ``tau_v`` and one ``window`` (n doubles or None) for both.  See solvers.Observations."""
+
+    def __init__(self, theta_u=None, tau_u=0.0, theta_v=None, tau_v=0.0, window=None):
+        self.theta_u, self.tau_u, self.theta_v, self.tau_v, self.window = theta_u, float(tau_u), theta_v, float(tau_v), window
+
+
+def _misfit(misfit) -> int:
+    if misfit not in MISFITS:
+        raise ValueError(f"Invalid value for 'misfit': '{misfit}'. Must be one of {sorted(MISFITS)}.")
+    return MISFITS[misfit]
+
+
 def dptr(x) -> int:
     """device address of a DeviceArray / torch tensor / raw int (None -> 0)."""
     if x is None:
@@ -482,10 +500,19 @@ class Context:
         check(self.handle, lib.femfct_nonlinear_forward_ct(self.handle, dptr(Aw), dptr(c_traj), int(bool(c_shared)), dptr(u),
                                                            int(num_steps), float(dt), float(eps), int(batch)))
 
-    def nonlinear_adjoint(self, Aw, u, uhat_T, p, num_steps, dt, eps, batch=1, alltime=False, uhat_shared=False):
+    def nonlinear_adjoint(self, Aw, u, uhat_T, p, num_steps, dt, eps, batch=1, alltime=False, uhat_shared=False, obs=None):
         """alltime=False: final-time misfit, uhat_T n values per member.  alltime=True: all-time misfit
         (nonlinear_FCT_PDECO_alltime.py:198-216), uhat_T a target trajectory per member ((num_steps+1)*n values, or one
-        for the whole batch with uhat_shared), p(T) = 0."""
+        for the whole batch with uhat_shared), p(T) = 0.  ``obs`` (a :class:`DeviceObs`; ``alltime`` is unused with it):
+        snapshot observations, uhat_T a trajectory per member read at observed levels only,
+        p_Nt = tau_u omega .* (uhat_Nt - u_Nt), load (theta_u[n]/dt) Mw (uhat_n - u_n)."""
+        if obs is not None:
+            if uhat_shared:
+                raise ValueError("uhat_shared: only the all-time sweep takes a shared target")
+            check(self.handle, lib.femfct_nonlinear_adjoint_obs(self.handle, dptr(Aw), dptr(u), dptr(uhat_T), dptr(obs.theta_u),
+                                                                obs.tau_u, dptr(obs.window), dptr(p), int(num_steps),
+                                                                float(dt), float(eps), int(batch)))
+            return
         if alltime:
             check(self.handle, lib.femfct_nonlinear_adjoint_alltime(self.handle, dptr(Aw), dptr(u), dptr(uhat_T),
                                                                     int(bool(uhat_shared)), dptr(p), int(num_steps),
@@ -513,9 +540,18 @@ class Context:
                                                         dptr(c_traj), int(bool(c_shared)), dptr(u), dptr(v), int(num_steps),
                                                         float(dt), _host_ptr(par), float(rescaling), int(batch)))
 
-    def schnak_adjoint(self, AwT, u, v, uhat_T, vhat_T, p, q, num_steps, dt, par, batch=1, alltime=False, wind_scale=None):
+    def schnak_adjoint(self, AwT, u, v, uhat_T, vhat_T, p, q, num_steps, dt, par, batch=1, alltime=False, wind_scale=None,
+                       obs=None):
+        """``obs`` (a :class:`DeviceObs`; ``alltime`` is unused with it): snapshot observations of u and v, the targets
+        trajectories read at observed levels only (None for a variable that is not observed)."""
         par = _as_f64(par)
         ws = None if wind_scale is None else _wind_scale(wind_scale, num_steps)
+        if obs is not None:
+            check(self.handle, lib.femfct_schnak_adjoint_obs(
+                self.handle, dptr(AwT), None if ws is None else _host_ptr(ws), dptr(u), dptr(v), dptr(uhat_T), dptr(vhat_T),
+                dptr(obs.theta_u), obs.tau_u, dptr(obs.theta_v), obs.tau_v, dptr(obs.window), dptr(p), dptr(q),
+                int(num_steps), float(dt), _host_ptr(par), int(batch)))
+            return
         check(self.handle, lib.femfct_schnak_adjoint_tw(self.handle, dptr(AwT), None if ws is None else _host_ptr(ws),
                                                         dptr(u), dptr(v), dptr(uhat_T), dptr(vhat_T), dptr(p), dptr(q),
                                                         int(num_steps), float(dt), _host_ptr(par), int(bool(alltime)),
@@ -548,9 +584,19 @@ class Context:
                                                        int(batch)))
 
     def chtxs_adjoint(self, u, v, uhat, vhat, p, q, c, num_steps, dt, par, rescaling=0.1, alltime=True, batch=1,
-                      growth=None):
-        """``growth``: as in :meth:`chtxs_forward`; the p step gains the explicit load of r'(u_n) p_{n+1}."""
+                      growth=None, obs=None, misfit="mass"):
+        """``growth``: as in :meth:`chtxs_forward`; the p step gains the explicit load of r'(u_n) p_{n+1}.
+        ``obs`` (a :class:`DeviceObs`; ``alltime`` is unused with it): snapshot observations; ``misfit="mass"`` loads
+        (theta[n]/dt) Mw (hat_n - state_n), the discrete adjoint of the tracking cost, ``"nodal"`` the raw nodal misfits
+        (theta[n]/dt) omega .* (hat_n - state_n) of the reference's all-time sweep."""
         par = _as_f64(par)
+        if obs is not None:
+            g = None if growth is None else _growth(growth)
+            check(self.handle, lib.femfct_chtxs_adjoint_obs(
+                self.handle, dptr(u), dptr(v), dptr(uhat), dptr(vhat), dptr(obs.theta_u), obs.tau_u, dptr(obs.theta_v),
+                obs.tau_v, dptr(obs.window), dptr(p), dptr(q), dptr(c), int(num_steps), float(dt), _host_ptr(par),
+                float(rescaling), None if g is None else _host_ptr(g), _misfit(misfit), int(batch)))
+            return
         if growth is not None:
             g = _growth(growth)
             check(self.handle, lib.femfct_chtxs_adjoint_g(self.handle, dptr(u), dptr(v), dptr(uhat), dptr(vhat), dptr(p),

@@ -6,6 +6,8 @@
 
 Each problem also runs with the other misfit (``optim=``); "nonlinear" with ``optim="alltime"`` and
 ``control_per_step=True`` is nonlinear_FCT_PDECO_alltime.py (p(T) = 0, misfit load in every adjoint step).
+``optim="snapshots"`` with ``obs=solvers.Observations(...)`` (extension) tracks each state at a few time levels,
+optionally on part of the domain: J = 1/2 sum_n w_n ||u_n - uhat_n||^2_Mw [+ the same for v] + beta/2 ||c||^2_Q.
 
 The loop, its constants, the line-search bookkeeping (fail counters, restarts, the control backup)
 and the order of the floating-point operations of the pointwise gradient follow the scripts; states,
@@ -25,7 +27,8 @@ import numpy as np
 
 from . import _lib
 from .mesh import SquareMeshP1
-from .systems import PDESystems, _chtxs_par, _schnak_par, get_nonlinear_eqns_params
+from .systems import (PDESystems, _chtxs_par, _schnak_par, get_nonlinear_eqns_params, split_observations,
+                      upload_observations)
 
 DEFAULTS = {
     # nonlinear_FCT_PDECO_refactored.py:49-65
@@ -50,19 +53,28 @@ class SystemPDECO:
     FunctionSpace); host vectors are in FEniCS DoF order like the reference's."""
 
     def __init__(self, problem: str, V: SquareMeshP1, num_steps: int, dt: float, device_id: int = 0, wind=None,
-                 wind_scale=None, control_per_step=False, growth=None, **overrides):
+                 wind_scale=None, control_per_step=False, growth=None, obs=None, misfit="mass", par=None, **overrides):
         """``wind`` / ``wind_scale`` (problem "schnak" only): the separable time-dependent wind ``s(t) w0(x)`` of the
         script BASELINE config 3 names (Schnak_FCT_PDECO_alltime.py:55,174-175), see systems.solve_schnak_system.
         ``control_per_step``: the state step to level n+1 reads control level n+1 (the all-time scripts, e.g.
         Schnak_FCT_PDECO_alltime.py:182-191) instead of level 1 for every step (helpers.py:577-578 etc.).
         ``growth=(r0, r1, r2)`` (problem "chtxs" only): cell growth r(u) = u (r0 + r1 u + r2 u^2) in the state and the
-        adjoint sweeps (systems.solve_chtxs_system); the gradient expression does not change."""
+        adjoint sweeps (systems.solve_chtxs_system); the gradient expression does not change.
+        ``optim="snapshots"`` with ``obs=`` one ``solvers.Observations`` for every state variable, or for the two-variable
+        problems a pair ``(obs_u, obs_v)`` one of which may be None (that variable is not observed, its target may be
+        None): the targets are trajectories read at the observed levels only.  ``misfit`` (problem "chtxs" only):
+        ``"mass"`` (default) loads the adjoint with Mw (hat_n - state_n), the discrete adjoint of the cost, ``"nodal"``
+        with the raw nodal misfits of the reference's all-time sweep (systems.solve_adjoint_chtxs_system).
+        ``par`` (problem "chtxs" only): ``(delta, Dm, Df, chi, eta)`` in the place of helpers.py:1197-1211's values, e.g.
+        those of chemotaxis_mimura_FCT_PGD.py."""
         if problem not in DEFAULTS:
             raise ValueError(f"unknown problem '{problem}' (one of {sorted(DEFAULTS)})")
         if (wind is not None or wind_scale is not None) and problem != "schnak":
             raise ValueError("wind / wind_scale: only the Schnakenberg driver has a time-dependent wind")
         if growth is not None and problem != "chtxs":
             raise ValueError("growth: only the chemotaxis driver has a growth term")
+        if par is not None and (problem != "chtxs" or len(par) != 5 or not np.all(np.isfinite(np.asarray(par, dtype=np.float64)))):
+            raise ValueError("par: the five finite chemotaxis parameters (delta, Dm, Df, chi, eta), problem 'chtxs' only")
         self.growth = growth
         self.problem, self.V, self.Nt, self.dt = problem, V, int(num_steps), float(dt)
         self.per_step = bool(control_per_step)
@@ -71,8 +83,18 @@ class SystemPDECO:
         if unknown:
             raise TypeError(f"unknown option(s) {sorted(unknown)}")
         self.P.update(overrides)
-        if self.P["optim"] not in ("alltime", "finaltime"):
+        if self.P["optim"] not in ("alltime", "finaltime", "snapshots"):
             raise ValueError(f"Invalid value for 'optim': '{self.P['optim']}'. Must be one of ['alltime', 'finaltime'].")
+        self.snap = self.P["optim"] == "snapshots"
+        if misfit not in ("mass", "nodal"):
+            raise ValueError(f"Invalid value for 'misfit': '{misfit}'. Must be one of ['mass', 'nodal'].")
+        if misfit != "mass" and (problem != "chtxs" or not self.snap):
+            raise ValueError("misfit: only the chemotaxis driver with optim='snapshots' has a choice of load")
+        if obs is not None and not self.snap:
+            raise ValueError("obs: only optim='snapshots' takes observations")
+        self.misfit = misfit
+        self.obs_pair = split_observations(obs, problem != "nonlinear", num_steps, V.nodes) if self.snap else None
+        self.obs_dev, self._obs_arrays = None, []
         self.S = PDESystems(V, device_id=device_id, order=_lib.ORDER_VERTEX)
         self.ctx, self.n = self.S.ctx, self.S.n
         self.tl = (self.Nt + 1) * self.n
@@ -88,7 +110,7 @@ class SystemPDECO:
             self.wscale = _wind_factors(wind_scale, self.Nt, self.dt)                               # forward: t += dt
             self.wscale_adj = _wind_factors(wind_scale, self.Nt, self.dt, T=self.Nt * self.dt)      # adjoint: t = T; t -= dt
         else:
-            self.par = _chtxs_par()
+            self.par = _chtxs_par() if par is None else [float(x) for x in par]
         self._arrays = []
 
     # ------------------------------------------------------------------ staging
@@ -116,10 +138,19 @@ class SystemPDECO:
         return out.ravel()
 
     def close(self):
-        for a in self._arrays:
+        for a in self._arrays + self._obs_arrays:
             a.free()
-        self._arrays = []
+        self._arrays, self._obs_arrays, self.obs_dev = [], [], None
         self.S.close()
+
+    def _obs(self):
+        """the observations on the device, uploaded once (window in the device's DoF order, cost weights per variable)"""
+        if self.obs_dev is None:
+            up = lambda w: self.ctx.array(np.ascontiguousarray(np.asarray(w, dtype=np.float64)[self.v2d]))
+            self.obs_dev, self._obs_arrays = upload_observations(self.ctx, self.obs_pair, up)
+            self.cost_w = [None if o is None else self.ctx.array(o.cost_w) for o in self.obs_pair[:2]]
+            self._obs_arrays += [a for a in self.cost_w if a is not None]
+        return self.obs_dev
 
     def __enter__(self):
         return self
@@ -153,17 +184,25 @@ class SystemPDECO:
             self.ctx.chtxs_forward(clev, u, v, self.Nt, self.dt, self.par, 0.1, batch=B, growth=self.growth)
 
     def _adjoint(self, u, v, p, q, c, tg):
+        obs = self._obs() if self.snap else None
         if self.problem == "nonlinear":
             self.ctx.nonlinear_adjoint(self.Aw, u, tg[0], p, self.Nt, self.dt, self.eps,
-                                       alltime=self.P["optim"] == "alltime")
+                                       alltime=self.P["optim"] == "alltime", obs=obs)
         elif self.problem == "schnak":
             self.ctx.schnak_adjoint(self.AwT, u, v, tg[0], tg[1], p, q, self.Nt, self.dt, self.par,
-                                    alltime=self.P["optim"] == "alltime", wind_scale=self.wscale_adj)
+                                    alltime=self.P["optim"] == "alltime", wind_scale=self.wscale_adj, obs=obs)
         else:
             self.ctx.chtxs_adjoint(u, v, tg[0], tg[1], p, q, c, self.Nt, self.dt, self.par, self.P["rescaling"],
-                                   self.P["optim"] == "alltime", growth=self.growth)
+                                   self.P["optim"] == "alltime", growth=self.growth, obs=obs, misfit=self.misfit)
 
     def _cost(self, u, v, c, tg, B=1):
+        if self.snap:       # the tracking term per observed variable, then the control term, every member in one call each
+            obs = self._obs()
+            J = 0.0
+            for x, t, w in ((u, tg[0], self.cost_w[0]), (v, tg[1] if self.two else None, self.cost_w[1])):
+                if w is not None:
+                    J = J + self.ctx.obs_cost(x, t, w, self.Nt, obs.window, batch=B)
+            return J + self.P["beta"] / 2 * self.ctx.l2_norm_sq_Q(c, None, self.Nt, self.dt, batch=B)
         return self.ctx.cost_functional(u, tg[0], c, self.Nt, self.dt, self.P["beta"], self.P["optim"],
                                         var2=v if self.two else None, var2_target=tg[1] if self.two else None, batch=B)
 
@@ -179,17 +218,22 @@ class SystemPDECO:
     # ------------------------------------------------------------------ the loop
     def run(self, ic, targets, speculative=True, callback=None):
         """ic = (u0,) / (u0, v0); targets = (uhat,) / (uhat, vhat): final-time vectors (n) or trajectories
-        ((Nt+1)*n) according to ``optim``.  Returns a dict: final u, v, p, q, c (NumPy, FEniCS order),
+        ((Nt+1)*n) according to ``optim`` (``"snapshots"``: trajectories, read at the observed levels only -- the rest
+        may hold anything, NaN included; None for a variable that is not observed).  Returns a dict: final u, v, p, q, c (NumPy, FEniCS order),
         ``cost`` (initial value first), ``armijo_its``, ``stop_crit``, ``it``, ``restored``."""
         P, ctx, n, tl, Nt, dt = self.P, self.ctx, self.n, self.tl, self.Nt, self.dt
         K = int(P["max_iter_armijo"])
         B = K if speculative else 1
-        tsz = tl if P["optim"] == "alltime" else n
+        tsz = tl if P["optim"] != "finaltime" else n
         if len(ic) != (2 if self.two else 1) or len(targets) != len(ic):
             raise ValueError("ic / targets: one entry per state variable")
+        if self.snap:       # a variable that is not observed has no target
+            targets = [t if o is not None else None for t, o in zip(targets, self.obs_pair[:2])]
         for t in targets:
-            if np.asarray(t).size != tsz:
-                raise ValueError(f"target of {np.asarray(t).size} values, expected {tsz} for optim='{P['optim']}'")
+            if self.snap and t is None:
+                continue
+            if t is None or np.asarray(t).size != tsz:
+                raise ValueError(f"target of {0 if t is None else np.asarray(t).size} values, expected {tsz} for optim='{P['optim']}'")
 
         def replicate(one, count, reps):
             """reps copies of a device vector, made on the device"""
@@ -209,14 +253,14 @@ class SystemPDECO:
         p = self._zeros(tl)
         q = self._zeros(tl) if self.two else None
         c, d, cbak = self._zeros(tl), self._zeros(tl), self._zeros(tl)
-        tg = [self._up(t) for t in targets]
+        tg = [None if t is None else self._up(t) for t in targets]
         clev = None if self.per_step else self._zeros(B * n)
         uB = traj0(ic[0], B)
         vB = traj0(ic[1], B) if self.two else None
         cB = self._zeros(B * tl)
         if speculative:
             ckB = self._zeros(B * tl)
-            tgB = [replicate(t, tsz, B) for t in tg]
+            tgB = [None if t is None else replicate(t, tsz, B) for t in tg]
         else:
             ckB, tgB = c, tg
 
@@ -316,8 +360,9 @@ class SystemPDECO:
 
 
 def projected_gradient_descent(problem, V, ic, targets, num_steps, dt, speculative=True, device_id=0, wind=None,
-                               wind_scale=None, control_per_step=False, growth=None, **overrides):
+                               wind_scale=None, control_per_step=False, growth=None, obs=None, misfit="mass", par=None,
+                               **overrides):
     """One call = one run of the refactored driver ``problem`` (see module docstring)."""
     with SystemPDECO(problem, V, num_steps, dt, device_id=device_id, wind=wind, wind_scale=wind_scale,
-                     control_per_step=control_per_step, growth=growth, **overrides) as prob:
+                     control_per_step=control_per_step, growth=growth, obs=obs, misfit=misfit, par=par, **overrides) as prob:
         return prob.run(ic, targets, speculative=speculative)

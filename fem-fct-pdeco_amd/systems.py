@@ -162,6 +162,65 @@ def _step_control(control, control_fun, nodes, num_steps, control_per_step):
     return c, True
 
 
+def split_observations(obs, two, num_steps, nodes):
+    """``obs`` of a snapshot sweep as ``(obs_u, obs_v, window)``: one ``solvers.Observations`` for every state variable, or
+    for a two-variable system a pair ``(obs_u, obs_v)`` in which one entry may be None (that variable is not observed).
+    Checked against ``num_steps`` and ``nodes``; the two share one window (host values, the problem's DoF order)."""
+    from .solvers import Observations
+    if isinstance(obs, Observations):
+        pair = (obs, obs if two else None)
+    elif isinstance(obs, (tuple, list)):
+        if not two:
+            raise ValueError("a pair of observations for the one-variable nonlinear problem: pass one Observations")
+        if len(obs) != 2 or not all(o is None or isinstance(o, Observations) for o in obs) or all(o is None for o in obs):
+            raise ValueError("obs must be an Observations or a pair (obs_u, obs_v) with at most one None")
+        pair = tuple(obs)
+    else:
+        raise ValueError("optim='snapshots' needs obs=Observations(...) or a pair (obs_u, obs_v)")
+    for o in pair:
+        if o is not None:
+            o.check(num_steps, nodes)
+    wins = [o.window for o in pair if o is not None]
+    if len(wins) == 2 and ((wins[0] is None) != (wins[1] is None) or
+                           (wins[0] is not None and not np.array_equal(wins[0], wins[1]))):
+        raise ValueError("the observations of the two variables must share one window")
+    return pair[0], pair[1], wins[0]
+
+
+def upload_observations(ctx, pair, up_window):
+    """:class:`device.DeviceObs` of ``split_observations``' result and its device arrays (to free); ``up_window`` uploads a
+    host nodal vector in the device's DoF order."""
+    from .device import DeviceObs
+    ou, ov, window = pair
+    arrays = []
+
+    def keep(a):
+        arrays.append(a)
+        return a
+    dev = DeviceObs(theta_u=None if ou is None else keep(ctx.array(ou.theta)), tau_u=0.0 if ou is None else ou.tau,
+                    theta_v=None if ov is None else keep(ctx.array(ov.theta)), tau_v=0.0 if ov is None else ov.tau,
+                    window=None if window is None else keep(up_window(window)))
+    return dev, arrays
+
+
+def _check_optim(optim, obs, two, num_steps, nodes, valid=("alltime", "finaltime")):
+    """the reference's message for an unknown mode; for ``optim="snapshots"`` the split observations, else None"""
+    if optim == "snapshots":
+        return split_observations(obs, two, num_steps, nodes)
+    if optim not in valid:
+        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of {list(valid)}.")
+    return None
+
+
+def _snapshot_target(t, observed, num_steps, nodes, name):
+    if not observed:
+        return None
+    if t is None or np.asarray(t).size != (num_steps + 1) * nodes:
+        raise ValueError(f"optim='snapshots': target {name} has {0 if t is None else np.asarray(t).size} values, expected "
+                         f"(num_steps + 1) * nodes = {(num_steps + 1) * nodes}")
+    return t
+
+
 class _Bufs:
     """Host (FEniCS DoF order, level-major) <-> device (vertex order) staging of one call."""
 
@@ -185,6 +244,12 @@ class _Bufs:
         d = self.ctx.zeros(count)
         self.items.append(d)
         return d
+
+    def obs(self, pair):
+        """the device side of split observations, freed with the rest"""
+        dev, arrays = upload_observations(self.ctx, pair, self.up)
+        self.items += [a for a in arrays if a not in self.items]
+        return dev
 
     def free(self):
         for d in self.items:
@@ -216,14 +281,16 @@ def solve_nonlinear_equation(control, var1, var2, V, nodes, num_steps, dt, dof_n
     return var1, None
 
 
-def solve_adjoint_nonlinear_equation(uk, uhat_T, pk, T, V, nodes, num_steps, dt, dof_neighbors, optim="finaltime"):
+def solve_adjoint_nonlinear_equation(uk, uhat_T, pk, T, V, nodes, num_steps, dt, dof_neighbors, optim="finaltime", *,
+                                     obs=None):
     """helpers.py:968-1038 (``optim="finaltime"``, the reference's signature and behaviour): fills ``pk`` (terminal
     condition included) and returns it.  ``optim="alltime"`` (extension, nonlinear_FCT_PDECO_alltime.py:198-216 with
     the HEAD operators): ``uhat_T`` is the target trajectory ((num_steps+1)*nodes values), p(T) = 0 and the step to
-    level n carries the misfit load ``assemble((uhat_n - u_n)*v*dx)``."""
-    if optim not in ("alltime", "finaltime"):
-        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
-    alltime = optim == "alltime"
+    level n carries the misfit load ``assemble((uhat_n - u_n)*v*dx)``.  ``optim="snapshots"`` with
+    ``obs=solvers.Observations(...)`` (extension): ``uhat_T`` is a trajectory read at the observed levels only,
+    p(T) = tau omega .* (uhat_T - u(T)) and the step to level n carries (theta_n/dt) Mw (uhat_n - u_n)."""
+    pair = _check_optim(optim, obs, False, num_steps, nodes)
+    alltime = optim != "finaltime"
     want = (num_steps + 1) * nodes if alltime else nodes
     if np.asarray(uhat_T).size != want:
         raise ValueError(f"optim='{optim}': target has {np.asarray(uhat_T).size} values, expected {want}")
@@ -233,7 +300,8 @@ def solve_adjoint_nonlinear_equation(uk, uhat_T, pk, T, V, nodes, num_steps, dt,
     B = _Bufs(S)
     try:
         p = B.up(pk)
-        S.ctx.nonlinear_adjoint(Aw, B.up(uk), B.up(uhat_T), p, num_steps, dt, eps, alltime=alltime)
+        S.ctx.nonlinear_adjoint(Aw, B.up(uk), B.up(uhat_T), p, num_steps, dt, eps, alltime=alltime,
+                                obs=None if pair is None else B.obs(pair))
         B.down(p, pk)
     finally:
         B.free()
@@ -304,22 +372,29 @@ def solve_schnak_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighb
 
 
 def solve_adjoint_schnak_system(uk, vk, uhat_T, vhat_T, pk, qk, T, V, nodes, num_steps, dt, dof_neighbors,
-                                optim="finaltime", wind=None, wind_scale=None):
+                                optim="finaltime", wind=None, wind_scale=None, *, obs=None):
     """helpers.py:599-698 (``optim="finaltime"``, the reference's signature and behaviour).
     ``optim="alltime"`` (extension, structure of Schnak_FCT_PDECO_alltime.py:204-284): the targets are
     trajectories, p(T) = q(T) = 0 and both equations carry the assembled misfit.
     ``wind`` / ``wind_scale``: as in :func:`solve_schnak_system`; the step that produces level n uses ``s(t_n)``
-    (helpers.py:664, 679: ``t -= dt; wind.t = t``)."""
-    if optim not in ("alltime", "finaltime"):
-        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+    (helpers.py:664, 679: ``t -= dt; wind.t = t``).
+    ``optim="snapshots"`` with ``obs=`` one ``solvers.Observations`` for both variables or a pair ``(obs_u, obs_v)``, one
+    of which may be None (extension): the targets are trajectories read at the observed levels only (None for a variable
+    that is not observed); terminal conditions tau omega .* (hat_T - state(T)), loads (theta_n/dt) Mw (hat_n - state_n)."""
+    pair = _check_optim(optim, obs, True, num_steps, nodes)
+    if pair is not None:
+        uhat_T = _snapshot_target(uhat_T, pair[0] is not None, num_steps, nodes, "u")
+        vhat_T = _snapshot_target(vhat_T, pair[1] is not None, num_steps, nodes, "v")
     S = _system(V)
     par, wind0 = _schnak_par()
     _, AwT = S.convection(wind or wind0, None if wind is not None else "schnak")
     B = _Bufs(S)
     try:
         p, q = B.up(pk), B.up(qk)
-        S.ctx.schnak_adjoint(AwT, B.up(uk), B.up(vk), B.up(uhat_T), B.up(vhat_T), p, q, num_steps, dt, par,
-                             alltime=optim == "alltime", wind_scale=_wind_factors(wind_scale, num_steps, dt, T=T))
+        S.ctx.schnak_adjoint(AwT, B.up(uk), B.up(vk), None if uhat_T is None else B.up(uhat_T),
+                             None if vhat_T is None else B.up(vhat_T), p, q, num_steps, dt, par,
+                             alltime=optim == "alltime", wind_scale=_wind_factors(wind_scale, num_steps, dt, T=T),
+                             obs=None if pair is None else B.obs(pair))
         B.down(p, pk)
         B.down(q, qk)
     finally:
@@ -381,18 +456,27 @@ def solve_chtxs_system(control, var1, var2, V, nodes, num_steps, dt, dof_neighbo
 
 def solve_adjoint_chtxs_system(uk, vk, uhat, vhat, pk, qk, control, T, V, nodes, num_steps, dt,
                                dof_neighbors, optim, show_plots=None, vertex_to_dof=None, out_folder=None,
-                               mesh=None, deltax=None, rescaling=1 / 10, *, growth=None):
+                               mesh=None, deltax=None, rescaling=1 / 10, *, growth=None, obs=None, misfit="mass"):
     """helpers.py:1387-1581.  ``growth``: as in :func:`solve_chtxs_system`; the p equation gains -r'(u) p, as the explicit
-    load assemble(r'(u_n)*p_{n+1}*w*dx) of the step to level n."""
+    load assemble(r'(u_n)*p_{n+1}*w*dx) of the step to level n.
+    ``optim="snapshots"`` with ``obs=`` as in :func:`solve_adjoint_schnak_system` (extension).  ``misfit="mass"`` (default)
+    loads (theta_n/dt) Mw (hat_n - state_n), the discrete adjoint of the tracking cost; ``misfit="nodal"`` loads the raw
+    nodal misfits (theta_n/dt) omega .* (hat_n - state_n) as the reference's all-time sweep does (helpers.py:1506-1507,
+    1533-1534), whose bits ``Observations.alltime`` then reproduces."""
     valid_options = ["alltime", "finaltime"]
-    if optim not in valid_options:
-        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of {valid_options}.")
+    pair = _check_optim(optim, obs, True, num_steps, nodes, valid_options)
+    if pair is not None:
+        from .device import _misfit
+        _misfit(misfit)
+        uhat = _snapshot_target(uhat, pair[0] is not None, num_steps, nodes, "u")
+        vhat = _snapshot_target(vhat, pair[1] is not None, num_steps, nodes, "v")
     S = _system(V)
     B = _Bufs(S)
     try:
         p, q = B.up(pk), B.up(qk)
-        S.ctx.chtxs_adjoint(B.up(uk), B.up(vk), B.up(uhat), B.up(vhat), p, q, B.up(control), num_steps, dt,
-                            _chtxs_par(), rescaling, optim == "alltime", growth=growth)
+        S.ctx.chtxs_adjoint(B.up(uk), B.up(vk), None if uhat is None else B.up(uhat), None if vhat is None else B.up(vhat),
+                            p, q, B.up(control), num_steps, dt, _chtxs_par(), rescaling, optim == "alltime", growth=growth,
+                            obs=None if pair is None else B.obs(pair), misfit=misfit)
         B.down(p, pk)
         B.down(q, qk)
     finally:

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct, femfct_nonlinear_adjoint_alltime, femfct_linear_trial_costs, femfct_source_trials, femfct_chtxs_{forward,adjoint}_g (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
+#define FEMFCT_ABI_VERSION 5   /* 5: femfct_build_id, FEMFCT_REGIME_MESH, femfct_{nonlinear,schnak,chtxs}_forward_ct, femfct_nonlinear_adjoint_alltime, femfct_linear_trial_costs, femfct_source_trials, femfct_chtxs_{forward,adjoint}_g, femfct_{nonlinear,schnak,chtxs}_adjoint_obs (added later, backward compatible); 4: femfct_patch_walkers; 3: femfct_kernel_regime, femfct_lowop_nonzero_fraction, femfct_chebsi_md, femfct_schnak_*_tw; 2: femfct_schnak_adjoint(alltime), species solver / PDECO / source-term entry points */
 
 typedef struct femfct_ctx femfct_ctx;
 
@@ -426,6 +426,35 @@ int femfct_chtxs_adjoint_g(femfct_ctx* ctx, const double* u_traj, const double* 
                            const double* vhat, double* p_traj, double* q_traj, const double* c_traj, int32_t num_steps,
                            double dt, const double* par, double rescaling, int32_t alltime, const double* growth,
                            int32_t batch);
+/* Snapshot observations for the three PDE systems (added after ABI version 5, backward compatible): the adjoint sweeps of
+ *   J = 1/2 sum_n w^u_n ||u_n - uhat_n||^2_Mw + 1/2 sum_n w^v_n ||v_n - vhat_n||^2_Mw + beta/2 ||c||^2_Q,
+ * Mw = assemble(omega_h*u*v*dx) (M without a window).  uhat/vhat_traj: (num_steps + 1)*n doubles per member, read at observed
+ * levels only.  theta_*_dev: num_steps + 1 doubles on the device, read per level inside the captured step (the values may
+ * change between sweeps); NULL: the variable is not observed and its target may be NULL.  Terminal conditions
+ * p_Nt = tau_u omega .* (uhat_Nt - u_Nt), q_Nt = tau_v omega .* (vhat_Nt - v_Nt), always written (zeros for tau = 0, the
+ * target's last level unread); the step to level n gains (theta_n/dt) Mw (hat_n - state_n) in the launches that carry the
+ * all-time misfits.  (tau, theta) = (1, 0) and (0, dt) without a window give the bits of the final-time and all-time sweeps;
+ * for chemotaxis with misfit = FEMFCT_MISFIT_NODAL, which loads (theta_n/dt) omega .* (hat_n - state_n) as helpers.py:1506-1507,
+ * 1533-1534 do; FEMFCT_MISFIT_MASS is the discrete adjoint load of J.  window_dev: n doubles or NULL.  A tau that is not
+ * finite or an unknown misfit: FEMFCT_ERR_INVALID.  Sweep kinds and budgets are those of the systems' adjoint sweeps (the
+ * nonlinear equation: its all-time kind). */
+#define FEMFCT_MISFIT_NODAL 0
+#define FEMFCT_MISFIT_MASS 1
+int femfct_nonlinear_adjoint_obs(femfct_ctx* ctx, const double* Aw_ell, const double* u_traj, const double* uhat_traj,
+                                 const double* theta_u_dev, double tau_u, const double* window_dev, double* p_traj,
+                                 int32_t num_steps, double dt, double eps, int32_t batch);
+/* wind_scale_host: as in femfct_schnak_adjoint_tw, NULL: stationary wind */
+int femfct_schnak_adjoint_obs(femfct_ctx* ctx, const double* AwT_ell, const double* wind_scale_host, const double* u_traj,
+                              const double* v_traj, const double* uhat_traj, const double* vhat_traj,
+                              const double* theta_u_dev, double tau_u, const double* theta_v_dev, double tau_v,
+                              const double* window_dev, double* p_traj, double* q_traj, int32_t num_steps, double dt,
+                              const double* par, int32_t batch);
+/* growth: as in femfct_chtxs_adjoint_g, NULL: none */
+int femfct_chtxs_adjoint_obs(femfct_ctx* ctx, const double* u_traj, const double* v_traj, const double* uhat_traj,
+                             const double* vhat_traj, const double* theta_u_dev, double tau_u, const double* theta_v_dev,
+                             double tau_v, const double* window_dev, double* p_traj, double* q_traj, const double* c_traj,
+                             int32_t num_steps, double dt, const double* par, double rescaling, const double* growth,
+                             int32_t misfit, int32_t batch);
 /* all-time misfit of the nonlinear equation (nonlinear_FCT_PDECO_alltime.py:198-216 with the HEAD operators of
  * helpers.py:1017-1037): p(T) = 0; for n = Nt-1..0:
  *   p_n = FCT_alg_ref(-Mat_p, M (uhat_n - u_n), p_{n+1}, non_flux_mat = M_u2(u_n) - M)
