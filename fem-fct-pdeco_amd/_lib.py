@@ -21,6 +21,7 @@ SOLVER_JACOBI, SOLVER_BICGSTAB = 0, 1
 REGIME_ROWS, REGIME_STRIPS, REGIME_TILE32, REGIME_PATCH64, REGIME_MESH = 0, 1, 2, 3, 4
 ABI_VERSION = 5
 MAX_TRIALS = 16          # FEMFCT_MAX_TRIALS: Armijo trials per femfct_linear_trial_costs / femfct_source_trials call
+MAX_MEMBERS = 256        # FEMFCT_MAX_MEMBERS: problems x trials per femfct_trial_controls / femfct_member_costs call
 
 
 class FemFctError(RuntimeError):
@@ -153,6 +154,8 @@ SIGNATURES = {
     "femfct_project_control": (C.c_int, [_p, _p, _d, _p, _d, _d, _p, C.c_int64]),
     "femfct_linear_trial_costs": (C.c_int, [_p, _p, _p, _p, _p, _p, _d, _i, _d, _d, _d, _i, _d, _i, _p, _p]),
     "femfct_source_trials": (C.c_int, [_p, _p, _p, _p, _d, _i, _d, _d, C.c_int64, _p, _p]),
+    "femfct_trial_controls": (C.c_int, [_p, _p, _p, _p, _i, _i, _d, _d, C.c_int64, _p]),
+    "femfct_member_costs": (C.c_int, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _d, _i, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -205,6 +205,112 @@ __global__ void k_source_trials(int64_t count, int K, const double* __restrict__
     }
 }
 
+// One double per member of a lockstep batch, passed by value in the kernel arguments (2 KiB): no device buffer to own,
+// fill or synchronise on.
+struct MemberTable { double v[FEMFCT_MAX_MEMBERS]; };
+
+// Lockstep trial controls: member m = p*K + t of P problems x K trials, c_out[m] = clip(c[p] + steps[m] * d[p]) with
+// k_clip_axpy's expression; c and d hold P blocks of count doubles (blockIdx.y strides the problems), c_out P*K.
+__global__ void k_trial_controls(int64_t count, int P, int K, const double* __restrict__ c, const double* __restrict__ d,
+                                 MemberTable steps, double lo, double hi, double* __restrict__ c_out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int p = blockIdx.y; p < P; p += gridDim.y) {
+        const double *cp = c + (int64_t)p * count, *dp = d + (int64_t)p * count;
+        double* op = c_out + (int64_t)p * K * count;
+        for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += stride) {
+            const double ck = cp[k], dk = dp[k];
+            for (int t = 0; t < K; ++t) op[t * count + k] = fmin(fmax(ck + steps.v[p * K + t] * dk, lo), hi);
+        }
+    }
+}
+
+// Costs of the members of a lockstep batch in one pass: for member m = p*K + t (u_m, c_m its trajectories, uhat_p / cref_p
+// its problem's target and reference control) and every (level, block) the three k_quadform partials
+//   misfit   phi = u_m - uhat_p    (every level; level Nt only, against the n-value target, when finaltime)
+//   control  phi = c_m - 0.0
+//   dist     phi = c_m - cref_p    (cref given)
+// A row reads its stencil of u_m, uhat_p, c_m, cref_p once and forms the three sums in registers.  Rows, expressions and
+// order are k_quadform's (block_rows partition, diagonal then slots 1..W-1, the same wave64 / LDS tree), as in
+// k_linear_trials, so the level folds over these partials give the bits of femfct_cost_functional / femfct_l2_norm_sq_Q on
+// each member alone.  (member, level) pairs are strided over gridDim.y (no 65535 cap).  Partials: misfit at
+// [m*plen_m + l*G + blk] (plen_m = G when finaltime, l = 0), control / dist at [(m*levels + l)*G + blk].
+__global__ void __launch_bounds__(256) k_member_costs(int n, int W, const int32_t* __restrict__ cols,
+                                                      const double* __restrict__ M, const double* __restrict__ u,
+                                                      const double* __restrict__ uhat, int64_t uhat_pstride,
+                                                      const double* __restrict__ c, const double* __restrict__ cref,
+                                                      int K, int levels, int64_t items, int finaltime,
+                                                      double* __restrict__ part_m, double* __restrict__ part_c,
+                                                      double* __restrict__ part_d) {
+    __shared__ double smem[3 * 4];      // 3 sums x up to 4 waves (blockDim <= 256)
+    const int G = gridDim.x;
+    const int nw = (blockDim.x + WAVE - 1) / WAVE, wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    const int64_t tl = (int64_t)levels * n;
+    RowRange rr = block_rows(n);
+    for (int64_t q = blockIdx.y; q < items; q += gridDim.y) {
+        const int m = (int)(q / levels), lvl = (int)(q % levels), p = m / K;
+        const bool mis = !finaltime || lvl == levels - 1;         // uniform over the block
+        const int64_t off = (int64_t)lvl * n;
+        const double *ul = u + m * tl + off, *cl = c + m * tl + off;
+        const double* hl = uhat + p * uhat_pstride + (finaltime ? 0 : off);
+        const double* rl = cref ? cref + p * tl + off : nullptr;
+        double sm = 0.0, sc = 0.0, sd = 0.0;
+        for (int i = rr.begin + threadIdx.x; i < rr.end; i += blockDim.x) {
+            const double mi = M[i], ci = cl[i];
+            const double pm = mis ? ul[i] - hl[i] : 0.0, pc = ci - 0.0, pd = rl ? ci - rl[i] : 0.0;
+            double am = mi * pm, ac = mi * pc, ad = mi * pd;
+            for (int k = 1; k < W; ++k) {
+                const int64_t idx = (int64_t)k * n + i;
+                const int j = cols[idx];
+                const double mk = M[idx], cj = cl[j];
+                if (mis) am += mk * (ul[j] - hl[j]);
+                ac += mk * (cj - 0.0);
+                if (rl) ad += mk * (cj - rl[j]);
+            }
+            sm += pm * am;
+            sc += pc * ac;
+            sd += pd * ad;
+        }
+        // block_reduce's tree for each of the three sums: wave butterflies, then the waves in order from 0.0
+        sm = wave_reduce(sm, OpSum());
+        sc = wave_reduce(sc, OpSum());
+        sd = wave_reduce(sd, OpSum());
+        if (nw > 1) {
+            __syncthreads();   // smem reuse across items
+            if (lane == 0) { smem[wid] = sm; smem[4 + wid] = sc; smem[8 + wid] = sd; }
+            __syncthreads();
+            double rm = 0.0, rc = 0.0, rd = 0.0;
+            for (int w = 0; w < nw; ++w) {
+                rm = rm + smem[w];
+                rc = rc + smem[4 + w];
+                rd = rd + smem[8 + w];
+            }
+            sm = rm; sc = rc; sd = rd;
+        }
+        if (threadIdx.x == 0) {
+            const int64_t pl = q * G + blockIdx.x;
+            if (mis) part_m[finaltime ? (int64_t)m * G + blockIdx.x : pl] = sm;
+            part_c[pl] = sc;
+            if (rl) part_d[pl] = sd;
+        }
+    }
+}
+
+// k_reduce_levels with one scale per batch member (the beta of a member's problem): out[b] (+)= scale.v[b] * sum ...
+__global__ void k_reduce_levels_member(int levels, int G, const double* __restrict__ partial, int trapezoid,
+                                       MemberTable scale, int accumulate, double* __restrict__ out) {
+    __shared__ double smem[32];
+    const int b = blockIdx.x;
+    const double* p = partial + (int64_t)b * levels * G;
+    double s = 0.0;
+    for (int64_t k = threadIdx.x; k < (int64_t)levels * G; k += blockDim.x) {
+        int l = (int)(k / G);
+        double w = (trapezoid && (l == 0 || l == levels - 1)) ? 0.5 : 1.0;
+        s += w * p[k];
+    }
+    s = block_reduce(s, OpSum(), 0.0, smem);
+    if (threadIdx.x == 0) out[b] = (accumulate ? out[b] : 0.0) + scale.v[b] * s;
+}
+
 int ensure_scratch(femfct_ctx* ctx, size_t doubles) {
     if (doubles <= ctx->scratch_count) return FEMFCT_OK;
     if (ctx->d_scratch) hipFree(ctx->d_scratch);
@@ -403,6 +509,69 @@ int femfct_source_trials(femfct_ctx* ctx, const double* c_dev, const double* d_d
     if (gr < 1) gr = 1;
     hipLaunchKernelGGL(k_source_trials, dim3((unsigned)gr), dim3(bs), 0, ctx->stream, count, (int)K, c_dev, d_dev, g_dev,
                        s0, c_lower, c_upper, c_out_dev, src_out_dev);
+    return FEMFCT_OK;
+}
+
+// ------------------------------------------------------------------------ lockstep batches: P problems x K trials
+int femfct_trial_controls(femfct_ctx* ctx, const double* c_dev, const double* d_dev, const double* steps_host, int32_t P,
+                          int32_t K, double c_lower, double c_upper, int64_t count, double* c_out_dev) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, c_dev && d_dev && steps_host && c_out_dev && count >= 0, "bad argument");
+    ARG_TRY(ctx, P >= 1 && K >= 1 && (int64_t)P * K <= FEMFCT_MAX_MEMBERS, "P*K (problems x trials) must be in 1..256");
+    MemberTable steps;
+    memset(&steps, 0, sizeof(steps));
+    memcpy(steps.v, steps_host, sizeof(double) * (size_t)(P * K));
+    int bs = 256;
+    int64_t gr = (count + bs - 1) / bs;
+    if (gr > 4096) gr = 4096;
+    if (gr < 1) gr = 1;
+    hipLaunchKernelGGL(k_trial_controls, dim3((unsigned)gr, (unsigned)P), dim3(bs), 0, ctx->stream, count, (int)P, (int)K,
+                       c_dev, d_dev, steps, c_lower, c_upper, c_out_dev);
+    return FEMFCT_OK;
+}
+
+int femfct_member_costs(femfct_ctx* ctx, const double* u_traj, const double* uhat, int32_t uhat_per_problem,
+                        const double* c_traj, const double* cref, const double* beta_host, int32_t P, int32_t K,
+                        int32_t num_steps, double dt, int32_t finaltime, double* J_host, double* dist_host) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx && ctx->n > 0 && ctx->have_mass, "mass matrix not set");
+    ARG_TRY(ctx, u_traj && uhat && c_traj && beta_host && J_host, "null argument");
+    ARG_TRY(ctx, !cref || dist_host, "cref needs dist_host");
+    ARG_TRY(ctx, uhat_per_problem == 0 || uhat_per_problem == 1, "uhat_per_problem must be 0 or 1");
+    ARG_TRY(ctx, P >= 1 && K >= 1 && (int64_t)P * K <= FEMFCT_MAX_MEMBERS, "P*K (problems x trials) must be in 1..256");
+    ARG_TRY(ctx, num_steps >= 1, "num_steps must be >= 1");
+    const int levels = num_steps + 1, members = P * K;
+    LaunchGeom g = femfct_geom(ctx, 1);
+    const int G = g.grid.x;
+    const size_t plen = (size_t)levels * G, plen_m = finaltime ? (size_t)G : plen;
+    int rc = ensure_scratch(ctx, (size_t)members * (plen_m + 2 * plen) + 2 * (size_t)members);
+    if (rc != FEMFCT_OK) return rc;
+    double* pm = ctx->d_scratch;
+    double* pc = pm + (size_t)members * plen_m;
+    double* pd = pc + (size_t)members * plen;
+    double* J = pd + (size_t)members * plen;
+    double* dist = J + members;
+    const int64_t items = (int64_t)levels * members, tl = (int64_t)levels * ctx->n;
+    g.grid.y = (unsigned)(items < 65535 ? items : 65535);
+    hipLaunchKernelGGL(k_member_costs, g.grid, g.block, 0, ctx->stream, ctx->n, ctx->W, ctx->d_cols, ctx->d_M, u_traj, uhat,
+                       uhat_per_problem ? (finaltime ? (int64_t)ctx->n : tl) : (int64_t)0, c_traj, cref, (int)K, levels,
+                       items, finaltime, pm, pc, pd);
+    // the level reductions and scale / accumulate order of femfct_cost_functional and femfct_l2_norm_sq_Q; the control
+    // term's scale 0.5 * beta * dt is formed here per member as femfct_cost_functional forms it
+    MemberTable scale;
+    memset(&scale, 0, sizeof(scale));
+    for (int m = 0; m < members; ++m) scale.v[m] = 0.5 * beta_host[m / K] * dt;
+    if (!finaltime)
+        hipLaunchKernelGGL(k_reduce_levels, dim3(members), dim3(256), 0, ctx->stream, levels, G, pm, 1, 0.5 * dt, 0, J);
+    else
+        hipLaunchKernelGGL(k_reduce_levels, dim3(members), dim3(256), 0, ctx->stream, 1, G, pm, 0, 0.5, 0, J);
+    hipLaunchKernelGGL(k_reduce_levels_member, dim3(members), dim3(256), 0, ctx->stream, levels, G, pc, 1, scale, 1, J);
+    HIP_TRY(ctx, hipMemcpyAsync(J_host, J, sizeof(double) * members, hipMemcpyDeviceToHost, ctx->stream));
+    if (cref) {
+        hipLaunchKernelGGL(k_reduce_levels, dim3(members), dim3(256), 0, ctx->stream, levels, G, pd, 1, dt, 0, dist);
+        HIP_TRY(ctx, hipMemcpyAsync(dist_host, dist, sizeof(double) * members, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return FEMFCT_OK;
 }
 

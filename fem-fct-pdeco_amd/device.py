@@ -463,6 +463,33 @@ class Context:
                                                     float(c_lower), float(c_upper), int(count), dptr(c_out),
                                                     dptr(src_out)))
 
+    def trial_controls(self, c, d, steps, P, K, c_lower, c_upper, count, c_out):
+        """Lockstep trial controls: c_out[p*K + t] = clip(c[p] + steps[p*K + t] * d[p]) for P problems x K trials (bitwise
+        P*K project_control calls), one launch; ``c``, ``d``: P blocks of ``count`` doubles, ``steps``: P*K host values."""
+        s = _as_f64(steps).reshape(-1)
+        if s.size != int(P) * int(K):
+            raise ValueError(f"trial_controls: {s.size} steps for P*K = {int(P) * int(K)} members")
+        check(self.handle, lib.femfct_trial_controls(self.handle, dptr(c), dptr(d), _host_ptr(s), int(P), int(K),
+                                                     float(c_lower), float(c_upper), int(count), dptr(c_out)))
+
+    def member_costs(self, u, uhat, c, betas, P, K, num_steps, dt, optim, cref=None, uhat_per_problem=False):
+        """J[m] = cost_functional(u_m, uhat_p, c_m, beta_p) and dist[m] = L2_norm_sq_Q(c_m - cref_p) of the P*K members
+        m = p*K + t of a lockstep batch, one fused pass (bitwise the two calls on each member alone).  ``uhat``: one target
+        or, with ``uhat_per_problem``, P; ``cref``: P reference controls or None.  Returns ``(J, dist)``, dist None
+        without ``cref``."""
+        if optim not in ("alltime", "finaltime"):
+            raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+        b = _as_f64(betas).reshape(-1)
+        if b.size != int(P):
+            raise ValueError(f"member_costs: {b.size} betas for P = {int(P)} problems")
+        members = max(int(P) * int(K), 1)
+        J = np.empty(members)
+        dist = None if cref is None else np.empty(members)
+        check(self.handle, lib.femfct_member_costs(
+            self.handle, dptr(u), dptr(uhat), int(bool(uhat_per_problem)), dptr(c), dptr(cref), _host_ptr(b), int(P), int(K),
+            int(num_steps), float(dt), int(optim == "finaltime"), _host_ptr(J), None if dist is None else _host_ptr(dist)))
+        return J, dist
+
     # -- non-FCT species / PDE systems ---------------------------------------------------
     def descent_pointwise(self, count, beta, c, x, out, y=None, scale=1.0, divisor=1.0):
         """out = -(beta*c - t), t = x*y/divisor (y given) or scale*x"""

@@ -504,6 +504,166 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
             a.free()
 
 
+class LockstepResult(list):
+    """What :func:`pgd_solidbody_lockstep` returns: the list of ``(u, p, c, hist)``, one per problem, with ``record``, the
+    launches of the run: per iteration ``problems`` (active problems = batch of the adjoint and first state sweep),
+    ``trials`` (members of the trial sweep) and the ``ctx.kernel_regime`` of both batches."""
+    record: dict
+
+
+def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c_upper, iters,
+                           gam=1e-4, s0=1.0, max_armijo=10, tol=None, optim="finaltime"):
+    """P projected-gradient loops of :func:`pgd_solidbody` (speculative form) carried in lockstep: problem p has the
+    regularisation ``betas[p]`` and, optionally, its own start control (``c0`` of shape (P, tlen); one (tlen,) control is
+    shared), first step length (``s0``: a scalar or P values) and target (``uhat``: one target or P).  The regularisation
+    sweep of advection_solidbody_FCT_PDECO_alltime.py:43-74 (one edited script copy per beta) as one loop.
+
+    Each iteration is pgd_solidbody's, statement for statement, for all active problems at once: one adjoint sweep and
+    one state sweep of P_active trajectories, one sweep of the P_active * max_armijo trial trajectories, the trial
+    controls and all costs / distances in one launch each (femfct_trial_controls, femfct_member_costs); the host makes
+    the Armijo decisions from the 2 * P_active * max_armijo scalars.  A batch member computes what it would compute alone,
+    so every problem follows its own pgd_solidbody run (to the low-order solver tolerance; P = 1 is that run, bit for bit).
+    A problem whose rel_change < ``tol`` is finished: its results are kept and it leaves all later launches.
+    Returns a :class:`LockstepResult`; each ``hist`` has pgd_solidbody's keys."""
+    if optim == "snapshots":
+        raise ValueError("optim='snapshots' is not yet carried by the lockstep loop (the snapshot cost takes one target per "
+                         "member); use pgd_solidbody_snapshots per problem")
+    if optim not in ("alltime", "finaltime"):
+        raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of ['alltime', 'finaltime'].")
+    alltime = optim == "alltime"
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    betas = np.asarray(betas, dtype=np.float64).ravel()
+    P, K = betas.size, int(max_armijo)
+    if P < 1:
+        raise ValueError("betas is empty: no problem to solve")
+    if K < 1 or P * K > _lib.MAX_MEMBERS:
+        raise ValueError(f"{P} problems x max_armijo = {K}: the product must be in 1..{_lib.MAX_MEMBERS}")
+    u0 = np.asarray(u0, dtype=np.float64).ravel()
+    if u0.size != n:
+        raise ValueError(f"u0 of {u0.size} values, expected {n}")
+    c0 = np.asarray(c0, dtype=np.float64)
+    if c0.shape == (tl,):
+        c0 = np.broadcast_to(c0, (P, tl))
+    elif c0.shape != (P, tl):
+        raise ValueError(f"c0 of shape {c0.shape}, expected ({tl},) or ({P}, {tl})")
+    s0 = np.asarray(s0, dtype=np.float64)
+    if s0.ndim == 0:
+        s0 = np.full(P, float(s0))
+    elif s0.shape != (P,):
+        raise ValueError(f"s0 of shape {s0.shape}, expected a scalar or ({P},)")
+    usz = tl if alltime else n
+    uhat = np.asarray(uhat, dtype=np.float64)
+    if uhat.shape == (P, usz) and P > 1:
+        per_problem = True
+    elif uhat.size == usz:
+        per_problem, uhat = False, uhat.reshape(usz)
+    else:
+        raise ValueError(f"target of shape {uhat.shape}, expected {usz} values or ({P}, {usz}) for optim='{optim}'")
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    at = lambda a, off: a.ptr + 8 * off          # device address of element ``off``
+    try:
+        u, p, d, c, rhs = alloc(P * tl), alloc(P * tl), alloc(P * tl), alloc(P * tl), alloc(P * tl, False)
+        c_prev = alloc(P * tl, False).upload(np.ascontiguousarray(c0))
+        uhP = alloc(P * usz, False)                 # a target per problem: what the adjoint sweep of P members reads
+        uhP.upload(np.ascontiguousarray(uhat if per_problem else np.broadcast_to(uhat, (P, usz))))
+        # (a shared target: the costs read the first copy; never a copy per trial)
+        cB, uB = alloc(P * K * tl), alloc(P * K * tl)
+        u0d = alloc(n, False).upload(u0)
+        for j in range(P):                          # level 0 of every trajectory = the initial condition
+            u.copy_from(u0d, n, dst_off=j * tl)
+        for m in range(P * K):
+            uB.copy_from(u0d, n, dst_off=m * tl)
+        for j in range(P):                          # the reference seeds u with the target before the first adjoint solve
+            if alltime:
+                u.copy_from(uhP, tl - n, dst_off=j * tl + n, src_off=j * tl + n)
+            else:
+                u.copy_from(uhP, n, dst_off=j * tl + Nt * n, src_off=j * n)
+        wall0 = time.perf_counter()
+        hists = [dict(cost=[], armijo_k=[], step=[], rel_change=[], armijo_margin=[], wall=[], wall0=wall0)
+                 for _ in range(P)]
+        results = [None] * P
+        record = dict(problems=[], trials=[], regime_problems=[], regime_trials=[])
+        act = list(range(P))                        # slot j of every buffer holds problem act[j]
+
+        def finish(j):
+            h = hists[act[j]]
+            h["armijo_margin_min"] = min((abs(m) for ms in h["armijo_margin"] for m in ms), default=None)
+            out = []
+            for a in (u, p, c_prev):
+                host = np.empty(tl)
+                _lib.check(ctx.handle, _lib.lib.femfct_memcpy_d2h(ctx.handle, host.ctypes.data, at(a, j * tl), 8 * tl))
+                out.append(host)
+            results[act[j]] = (*out, h)
+
+        for it in range(iters):
+            Pa = len(act)
+            if Pa == 0:
+                break
+            b_act, s_act = betas[act], s0[act]
+            record["problems"].append(Pa)
+            record["trials"].append(Pa * K)
+            record["regime_problems"].append(ctx.kernel_regime(Pa))
+            record["regime_trials"].append(ctx.kernel_regime(Pa * K))
+            prob.adjoint(c_prev, u, uhP, p, optim, batch=Pa)
+            for j in range(Pa):
+                ctx.drift_gradient_rhs(at(c_prev, j * tl), at(u, j * tl), at(p, j * tl), b_act[j], at(rhs, j * tl), Nt + 1,
+                                       prob.drift)
+            ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=(Nt + 1) * Pa)
+            ctx.trial_controls(c_prev, d, s_act, Pa, 1, c_lower, c_upper, tl, c)
+            prob.forward(c, u, batch=Pa)
+            J_k, _ = ctx.member_costs(u, uhP, c, b_act, Pa, 1, Nt, dt, optim,
+                                      uhat_per_problem=per_problem)
+            svals = [[float(s) * (1 / 2 ** k) for k in range(K)] for s in s_act]
+            ctx.trial_controls(c, d, np.array(svals), Pa, K, c_lower, c_upper, tl, cB)
+            prob.forward(cB, uB, batch=Pa * K)
+            J, stat = ctx.member_costs(uB, uhP, cB, b_act, Pa, K, Nt, dt, optim, cref=c,
+                                       uhat_per_problem=per_problem)
+            now = time.perf_counter()               # (J is a read-back: the iteration's device work is done)
+            done = []
+            for j in range(Pa):
+                Jk, h, margins, accepted = float(J_k[j]), hists[act[j]], [], None
+                for k, s in enumerate(svals[j]):
+                    accepted, m = k, j * K + k
+                    margins.append((float(J[m]) - Jk + gam / s * float(stat[m])) / abs(Jk))
+                    if not (J[m] - Jk > -gam / s * stat[m]):
+                        break
+                m = j * K + accepted
+                J_acc = float(J[m])
+                c_prev.copy_from(cB, tl, dst_off=j * tl, src_off=m * tl)
+                u.copy_from(uB, tl, dst_off=j * tl, src_off=m * tl)
+                h["cost"].append(J_acc)
+                h["wall"].append(now)
+                h["armijo_margin"].append(margins)
+                h["armijo_k"].append(accepted + 1)
+                h["step"].append(svals[j][accepted])
+                h["rel_change"].append(abs(Jk - J_acc) / abs(Jk))
+                if tol is not None and h["rel_change"][-1] < tol:
+                    done.append(j)
+            if done:                                # keep the finished problems' results, close the ranks of the others
+                for j in done:
+                    finish(j)
+                keep = [j for j in range(Pa) if j not in done]
+                for jn, jo in enumerate(keep):
+                    if jn != jo:                    # (jn < jo: slots are disjoint blocks)
+                        for a, sz in ((u, tl), (p, tl), (c_prev, tl)) + (((uhP, usz),) if per_problem else ()):
+                            a.copy_from(a, sz, dst_off=jn * sz, src_off=jo * sz)
+                act = [act[j] for j in keep]
+        for j in range(len(act)):
+            finish(j)
+        out = LockstepResult(results)
+        out.record = record
+        return out
+    finally:
+        for a in bufs:
+            a.free()
+
+
 def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
                        increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None):
     """Projected gradient descent for the linear source-control problem, the loop of

@@ -329,6 +329,23 @@ int femfct_source_trials(femfct_ctx* ctx, const double* c_dev, const double* d_d
                          int32_t K, double c_lower, double c_upper, int64_t count, double* c_out_dev,
                          double* src_out_dev);
 
+/* Lockstep batches of the drift-control PGD (config C5's regularisation sweep as one loop): P problems, each with K
+ * Armijo trials, advance together; member m = p*K + t stands for problem p < P and trial t < K, 1 <= P*K <= 256. */
+#define FEMFCT_MAX_MEMBERS 256
+/* c_out[m*count + k] = clip(c[p*count + k] + steps_host[p*K + t] * d[p*count + k], c_lower, c_upper): bitwise what P*K
+ * calls of femfct_project_control write (c, d: P blocks of count doubles; c_out: P*K; must not alias them).  The steps
+ * are read before the call returns.  One launch, does not synchronise. */
+int femfct_trial_controls(femfct_ctx* ctx, const double* c_dev, const double* d_dev, const double* steps_host, int32_t P,
+                          int32_t K, double c_lower, double c_upper, int64_t count, double* c_out_dev);
+/* J_host[m] = cost_functional(u_m, uhat_p, c_m, ..., beta_host[p], finaltime) and dist_host[m] = L2_norm_sq_Q(c_m - cref_p)
+ * for the P*K member trajectories u_traj / c_traj ((num_steps+1)*n doubles each), bitwise what femfct_cost_functional and
+ * femfct_l2_norm_sq_Q return for each member alone, in one fused pass; levels * members is not limited.  uhat: one target
+ * (uhat_per_problem = 0) or P (1), each n doubles when finaltime, else a trajectory.  cref: P reference controls, or NULL
+ * (no distances; dist_host may be NULL).  Synchronises. */
+int femfct_member_costs(femfct_ctx* ctx, const double* u_traj, const double* uhat, int32_t uhat_per_problem,
+                        const double* c_traj, const double* cref, const double* beta_host, int32_t P, int32_t K,
+                        int32_t num_steps, double dt, int32_t finaltime, double* J_host, double* dist_host);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
