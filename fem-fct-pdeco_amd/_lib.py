@@ -156,6 +156,8 @@ SIGNATURES = {
     "femfct_source_trials": (C.c_int, [_p, _p, _p, _p, _d, _i, _d, _d, C.c_int64, _p, _p]),
     "femfct_trial_controls": (C.c_int, [_p, _p, _p, _p, _i, _i, _d, _d, C.c_int64, _p]),
     "femfct_member_costs": (C.c_int, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _d, _i, _p, _p]),
+    "femfct_time_restrict": (C.c_int, [_p, _p, _p, _i, _i, _i, _p]),
+    "femfct_time_prolong": (C.c_int, [_p, _p, _p, _i, _i, _i, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -228,6 +228,10 @@ struct femfct_ctx {
     // scratch for reductions (kernels_pgd.hip)
     double* d_scratch = nullptr;
     size_t scratch_count = 0;
+    // table of the time intervals of femfct_time_restrict / femfct_time_prolong, and its host copy (kernels_pgd.hip)
+    int32_t* d_ttab = nullptr;
+    size_t ttab_count = 0;
+    std::vector<int32_t> h_ttab;
 };
 
 // error helpers ---------------------------------------------------------------

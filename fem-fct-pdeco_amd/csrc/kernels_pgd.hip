@@ -576,3 +576,188 @@ int femfct_member_costs(femfct_ctx* ctx, const double* u_traj, const double* uha
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------ controls piecewise constant in time
+// K intervals of time levels, interval k = the levels starts[k] <= l < starts[k+1] (starts[0] = 0, starts[K] = levels).
+// With the trapezoid's level weights w_l (1, and 1/2 at the first and last level; dt cancels) and W_k = sum_{l in k} w_l
+//   restrict(x)[k] = (sum_{l in k} w_l x_l) / W_k      one field of n values per interval
+//   prolong(y)[l]  = y[k(l)]
+// prolong(restrict(.)) is the L2(Q)-orthogonal projection (the inner product of femfct_l2_norm_sq_Q) onto the controls
+// that are constant in time on every interval.
+//
+// k_time_restrict is a column sum: lane = node (unit-stride loads), the levels of an interval are cut into chunks of
+// TR_CH, one block each, and a chunk into runs of TR_LW levels, one wave each.  A wave sums its run in level order in a
+// register (the TR_LW loads are independent), wave 0 adds the runs of its chunk in order through LDS, and where an
+// interval has more than one chunk k_time_restrict_fold adds the chunk sums in order from a partials buffer.  The order
+// of an interval's sum depends on its length alone: no atomics, the same bits for every batch size, member and run.  An
+// interval of one level gives (w x) / w = x exactly.
+#define TR_LW 8
+#define TR_CH 32
+
+namespace {
+
+// Device table of a set of intervals (int32): starts[K+1], first work item of interval k [K+1], first partial of
+// interval k [K+1] (an interval of one chunk has none), interval of work item j [items], interval of level l [levels].
+struct TimeTable { const int32_t *starts, *ifirst, *pfirst, *item_k, *level_k; int K, items, nparts, maxlen; };
+
+__device__ __forceinline__ double trapezoid_w(int l, int levels) { return (l == 0 || l == levels - 1) ? 0.5 : 1.0; }
+__device__ __forceinline__ double interval_weight(int s, int e, int levels) {
+    return (double)(e - s) - (s == 0 ? 0.5 : 0.0) - (e == levels ? 0.5 : 0.0);
+}
+
+// blockDim.x = 256, or 64 when no interval is longer than TR_LW; work = batch * items, strided over gridDim.y
+__global__ void __launch_bounds__(256) k_time_restrict(int n, int levels, TimeTable t, int64_t work,
+                                                       const double* __restrict__ x, double* __restrict__ out,
+                                                       double* __restrict__ part) {
+    __shared__ double smem[(TR_CH / TR_LW) * WAVE];
+    const int wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    const int i = blockIdx.x * WAVE + lane;
+    for (int64_t q = blockIdx.y; q < work; q += gridDim.y) {
+        const int64_t b = q / t.items;
+        const int it = (int)(q % t.items), k = t.item_k[it], c = it - t.ifirst[k];
+        const int s = t.starts[k], e = t.starts[k + 1];
+        const int c0 = s + c * TR_CH, c1 = min(c0 + TR_CH, e);      // this block's chunk
+        const int used = (c1 - c0 + TR_LW - 1) / TR_LW;              // waves with a run (uniform over the block)
+        const int l0 = c0 + wid * TR_LW, l1 = min(l0 + TR_LW, c1);
+        double acc = 0.0;
+        if (i < n && l0 < l1) {
+            const double* xp = x + b * levels * n + i;
+            double v[TR_LW];
+#pragma unroll
+            for (int j = 0; j < TR_LW; ++j) v[j] = l0 + j < l1 ? xp[(int64_t)(l0 + j) * n] : 0.0;
+            acc = trapezoid_w(l0, levels) * v[0];
+#pragma unroll
+            for (int j = 1; j < TR_LW; ++j)
+                if (l0 + j < l1) acc += trapezoid_w(l0 + j, levels) * v[j];
+        }
+        if (used > 1) {
+            __syncthreads();   // smem reuse across work items
+            smem[wid * WAVE + lane] = acc;
+            __syncthreads();
+            if (wid == 0) {
+                acc = smem[lane];
+                for (int w = 1; w < used; ++w) acc += smem[w * WAVE + lane];
+            }
+        }
+        if (wid == 0 && i < n) {
+            if (e - s <= TR_CH) out[(b * t.K + k) * n + i] = acc / interval_weight(s, e, levels);
+            else part[(b * t.nparts + t.pfirst[k] + c) * n + i] = acc;
+        }
+    }
+}
+
+// the intervals of more than one chunk: out = (chunk sums, added in order) / W_k; work = batch * K over gridDim.y
+__global__ void k_time_restrict_fold(int n, int levels, TimeTable t, int64_t work, const double* __restrict__ part,
+                                     double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int64_t q = blockIdx.y; q < work; q += gridDim.y) {
+        const int64_t b = q / t.K;
+        const int k = (int)(q % t.K), s = t.starts[k], e = t.starts[k + 1];
+        if (e - s <= TR_CH) continue;
+        const int nch = (e - s + TR_CH - 1) / TR_CH;
+        const double* p = part + (b * t.nparts + t.pfirst[k]) * n + i;
+        double acc = p[0];
+        for (int c = 1; c < nch; ++c) acc += p[(int64_t)c * n];
+        out[(b * t.K + k) * n + i] = acc / interval_weight(s, e, levels);
+    }
+}
+
+// out[b][l] = y[b][k(l)]; work = batch * levels over gridDim.y
+__global__ void k_time_prolong(int n, int levels, TimeTable t, int64_t work, const double* __restrict__ y,
+                               double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int64_t q = blockIdx.y; q < work; q += gridDim.y) {
+        const int64_t b = q / levels;
+        const int l = (int)(q % levels);
+        out[q * n + i] = y[(b * t.K + t.level_k[l]) * n + i];
+    }
+}
+
+// Checks ``starts`` and makes the intervals' table resident on the device (uploaded when it differs from the one there).
+int time_table(femfct_ctx* ctx, const int32_t* starts, int32_t K, int32_t levels, TimeTable* t) {
+    ARG_TRY(ctx, starts && K >= 1 && K <= levels, "starts: K + 1 levels with 1 <= K <= num_steps + 1");
+    ARG_TRY(ctx, starts[0] == 0 && starts[K] == levels, "starts must begin at 0 and end at num_steps + 1");
+    for (int k = 0; k < K; ++k) ARG_TRY(ctx, starts[k] < starts[k + 1], "starts must be strictly increasing");
+    std::vector<int32_t> h(starts, starts + K + 1), ifirst(K + 1), pfirst(K + 1), item_k, level_k(levels);
+    int items = 0, nparts = 0, maxlen = 0;
+    for (int k = 0; k < K; ++k) {
+        const int len = starts[k + 1] - starts[k], nch = (len + TR_CH - 1) / TR_CH;
+        ifirst[k] = items;
+        pfirst[k] = nparts;
+        items += nch;
+        if (nch > 1) nparts += nch;
+        if (len > maxlen) maxlen = len;
+        item_k.insert(item_k.end(), nch, k);
+        for (int l = starts[k]; l < starts[k + 1]; ++l) level_k[l] = k;
+    }
+    ifirst[K] = items;
+    pfirst[K] = nparts;
+    h.insert(h.end(), ifirst.begin(), ifirst.end());
+    h.insert(h.end(), pfirst.begin(), pfirst.end());
+    h.insert(h.end(), item_k.begin(), item_k.end());
+    h.insert(h.end(), level_k.begin(), level_k.end());
+    if (h != ctx->h_ttab) {
+        if (h.size() > ctx->ttab_count) {
+            if (ctx->d_ttab) hipFree(ctx->d_ttab);
+            ctx->d_ttab = nullptr;
+            ctx->ttab_count = 0;
+            ctx->h_ttab.clear();
+            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ttab, sizeof(int32_t) * h.size()));
+            ctx->ttab_count = h.size();
+        }
+        ctx->h_ttab.clear();      // (stays empty, and the next call uploads again, should the copy fail)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ttab, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice, ctx->stream));
+        ctx->h_ttab.swap(h);
+    }
+    const int32_t* d = ctx->d_ttab;
+    *t = TimeTable{d, d + (K + 1), d + 2 * (K + 1), d + 3 * (K + 1), d + 3 * (K + 1) + items, K, items, nparts, maxlen};
+    return FEMFCT_OK;
+}
+
+unsigned grid_y(int64_t work) { return (unsigned)(work < 65535 ? work : 65535); }
+
+}  // namespace
+
+extern "C" {
+
+int femfct_time_restrict(femfct_ctx* ctx, const double* x_traj, const int32_t* starts_host, int32_t K, int32_t num_steps,
+                         int32_t batch, double* out_dev) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx->n > 0, "pattern not set");
+    ARG_TRY(ctx, x_traj && out_dev && num_steps >= 1 && batch >= 1, "bad argument");
+    const int levels = num_steps + 1, n = ctx->n;
+    TimeTable t;
+    int rc = time_table(ctx, starts_host, K, levels, &t);
+    if (rc != FEMFCT_OK) return rc;
+    if (t.nparts) {
+        rc = ensure_scratch(ctx, (size_t)batch * t.nparts * n);
+        if (rc != FEMFCT_OK) return rc;
+    }
+    const unsigned tiles = (unsigned)((n + WAVE - 1) / WAVE);
+    const int64_t work = (int64_t)batch * t.items;
+    hipLaunchKernelGGL(k_time_restrict, dim3(tiles, grid_y(work)), dim3(t.maxlen <= TR_LW ? WAVE : 256), 0, ctx->stream, n,
+                       levels, t, work, x_traj, out_dev, ctx->d_scratch);
+    if (t.nparts)
+        hipLaunchKernelGGL(k_time_restrict_fold, dim3((unsigned)((n + 255) / 256), grid_y((int64_t)batch * K)), dim3(256), 0,
+                           ctx->stream, n, levels, t, (int64_t)batch * K, ctx->d_scratch, out_dev);
+    return FEMFCT_OK;
+}
+
+int femfct_time_prolong(femfct_ctx* ctx, const double* y_dev, const int32_t* starts_host, int32_t K, int32_t num_steps,
+                        int32_t batch, double* out_traj) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx->n > 0, "pattern not set");
+    ARG_TRY(ctx, y_dev && out_traj && num_steps >= 1 && batch >= 1, "bad argument");
+    const int levels = num_steps + 1, n = ctx->n;
+    TimeTable t;
+    int rc = time_table(ctx, starts_host, K, levels, &t);
+    if (rc != FEMFCT_OK) return rc;
+    const int64_t work = (int64_t)batch * levels;
+    hipLaunchKernelGGL(k_time_prolong, dim3((unsigned)((n + 255) / 256), grid_y(work)), dim3(256), 0, ctx->stream, n, levels,
+                       t, work, y_dev, out_traj);
+    return FEMFCT_OK;
+}
+
+}  // extern "C"

@@ -490,6 +490,33 @@ class Context:
             int(num_steps), float(dt), int(optim == "finaltime"), _host_ptr(J), None if dist is None else _host_ptr(dist)))
         return J, dist
 
+    # -- controls piecewise constant in time (solvers.ControlIntervals) --------------------
+    @staticmethod
+    def _starts(starts, num_steps):
+        s = np.ascontiguousarray(np.asarray(starts).reshape(-1), dtype=np.int32)
+        if s.size < 2:
+            raise ValueError("starts: K + 1 >= 2 interval boundaries are needed")
+        return s, s.size - 1
+
+    def time_restrict(self, x, starts, num_steps, out, batch=1):
+        """out[b][k] = the trapezoid-weighted time mean of x[b] over the levels starts[k] <= l < starts[k+1], for the
+        ``batch`` trajectories x ((num_steps+1)*n doubles each); ``out``: batch*K*n doubles.  Does not synchronise."""
+        s, K = self._starts(starts, num_steps)
+        check(self.handle, lib.femfct_time_restrict(self.handle, dptr(x), _host_ptr(s), K, int(num_steps), int(batch),
+                                                    dptr(out)))
+
+    def time_prolong(self, y, starts, num_steps, out, batch=1):
+        """out[b][l] = y[b][k(l)]: the K fields of every member held over their intervals (``out`` must not be ``y``)."""
+        s, K = self._starts(starts, num_steps)
+        check(self.handle, lib.femfct_time_prolong(self.handle, dptr(y), _host_ptr(s), K, int(num_steps), int(batch),
+                                                   dptr(out)))
+
+    def time_project(self, x, starts, num_steps, scratch, batch=1):
+        """x <- prolong(restrict(x)) in place, the L2(Q)-orthogonal projection onto the trajectories constant on every
+        interval; ``scratch``: batch*K*n doubles."""
+        self.time_restrict(x, starts, num_steps, scratch, batch)
+        self.time_prolong(scratch, starts, num_steps, x, batch)
+
     # -- non-FCT species / PDE systems ---------------------------------------------------
     def descent_pointwise(self, count, beta, c, x, out, y=None, scale=1.0, divisor=1.0):
         """out = -(beta*c - t), t = x*y/divisor (y given) or scale*x"""

@@ -18,6 +18,11 @@ agree to the solver tolerance) -- the lever that fills the GPU on these small me
 ``control_per_step=True`` steps the state with the control of the level being computed (the step to
 level n+1 reads level n+1), as the reference's all-time scripts do; by default the state solvers
 freeze the control at level 1 like helpers.py (see systems.py).
+``control_time=solvers.ControlIntervals(...)`` (extension) holds the control constant in time on K intervals: the
+pointwise direction is projected onto these controls.  With the default frozen sweep the state depends on one spatial
+field only, so the problem posed is a stationary control and K = 1 (``ControlIntervals.stationary``) is its consistent
+pairing: the projected direction is the time average of the pointwise expression, the gradient with respect to that one
+field, where the free loop moves level 1 by its own slice and every other level by the regularisation alone.
 """
 from __future__ import annotations
 
@@ -53,7 +58,8 @@ class SystemPDECO:
     FunctionSpace); host vectors are in FEniCS DoF order like the reference's."""
 
     def __init__(self, problem: str, V: SquareMeshP1, num_steps: int, dt: float, device_id: int = 0, wind=None,
-                 wind_scale=None, control_per_step=False, growth=None, obs=None, misfit="mass", par=None, **overrides):
+                 wind_scale=None, control_per_step=False, growth=None, obs=None, misfit="mass", par=None,
+                 control_time=None, **overrides):
         """``wind`` / ``wind_scale`` (problem "schnak" only): the separable time-dependent wind ``s(t) w0(x)`` of the
         script BASELINE config 3 names (Schnak_FCT_PDECO_alltime.py:55,174-175), see systems.solve_schnak_system.
         ``control_per_step``: the state step to level n+1 reads control level n+1 (the all-time scripts, e.g.
@@ -66,7 +72,9 @@ class SystemPDECO:
         ``"mass"`` (default) loads the adjoint with Mw (hat_n - state_n), the discrete adjoint of the cost, ``"nodal"``
         with the raw nodal misfits of the reference's all-time sweep (systems.solve_adjoint_chtxs_system).
         ``par`` (problem "chtxs" only): ``(delta, Dm, Df, chi, eta)`` in the place of helpers.py:1197-1211's values, e.g.
-        those of chemotaxis_mimura_FCT_PGD.py."""
+        those of chemotaxis_mimura_FCT_PGD.py.
+        ``control_time`` (a ``solvers.ControlIntervals``): the control is constant in time on its K intervals (see the
+        module docstring).  K > 1 needs ``control_per_step=True``: the frozen sweep reads one level only."""
         if problem not in DEFAULTS:
             raise ValueError(f"unknown problem '{problem}' (one of {sorted(DEFAULTS)})")
         if (wind is not None or wind_scale is not None) and problem != "schnak":
@@ -78,6 +86,12 @@ class SystemPDECO:
         self.growth = growth
         self.problem, self.V, self.Nt, self.dt = problem, V, int(num_steps), float(dt)
         self.per_step = bool(control_per_step)
+        if control_time is not None:
+            control_time.check(num_steps)
+            if control_time.K > 1 and not self.per_step:
+                raise ValueError(f"control_time with K = {control_time.K} intervals needs control_per_step=True: the default "
+                                 "state sweep freezes the control at level 1 and reads one level only (K = 1 fits it)")
+        self.control_time = control_time
         self.P = dict(DEFAULTS[problem])
         unknown = set(overrides) - set(self.P)
         if unknown:
@@ -112,6 +126,7 @@ class SystemPDECO:
         else:
             self.par = _chtxs_par() if par is None else [float(x) for x in par]
         self._arrays = []
+        self._ct_fields = None      # the K fields of a projected direction (control_time)
 
     # ------------------------------------------------------------------ staging
     def _up(self, x, count=None):
@@ -214,6 +229,11 @@ class SystemPDECO:
             self.ctx.descent_pointwise(self.tl, beta, c, p, d, scale=self.par[3] / r)   # -(beta*ck - gamma/r*pk)
         else:
             self.ctx.descent_pointwise(self.tl, beta, c, q, d, y=u, divisor=r)       # -(beta*ck - qk*uk/r)
+        ct = self.control_time
+        if ct is not None:      # the start control is 0, so every iterate clip(c + s P d) is constant on the intervals
+            if self._ct_fields is None:
+                self._ct_fields = self.ctx.empty(ct.K * self.n)
+            self.ctx.time_project(d, ct.starts, self.Nt, self._ct_fields)
 
     # ------------------------------------------------------------------ the loop
     def run(self, ic, targets, speculative=True, callback=None):
@@ -361,8 +381,9 @@ class SystemPDECO:
 
 def projected_gradient_descent(problem, V, ic, targets, num_steps, dt, speculative=True, device_id=0, wind=None,
                                wind_scale=None, control_per_step=False, growth=None, obs=None, misfit="mass", par=None,
-                               **overrides):
+                               control_time=None, **overrides):
     """One call = one run of the refactored driver ``problem`` (see module docstring)."""
     with SystemPDECO(problem, V, num_steps, dt, device_id=device_id, wind=wind, wind_scale=wind_scale,
-                     control_per_step=control_per_step, growth=growth, obs=obs, misfit=misfit, par=par, **overrides) as prob:
+                     control_per_step=control_per_step, growth=growth, obs=obs, misfit=misfit, par=par,
+                     control_time=control_time, **overrides) as prob:
         return prob.run(ic, targets, speculative=speculative)

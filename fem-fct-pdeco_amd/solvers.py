@@ -126,6 +126,104 @@ def _need_obs(optim, obs):
     return optim == "snapshots"
 
 
+class ControlIntervals:
+    """Controls that are piecewise constant in time: K intervals of time levels, interval k = the levels
+    ``starts[k] <= l < starts[k+1]`` (K + 1 increasing integers, ``starts[0] = 0``, ``starts[K] = num_steps + 1``).
+
+    Passed as ``control_time=`` to a projected-gradient loop, the descent direction is projected onto these controls,
+    d <- P d with P = prolong o restrict,
+
+        restrict(x)[k] = (sum_{l in k} w_l x_l) / W_k,   W_k = sum_{l in k} w_l,      prolong(y)[l] = y[k(l)]
+
+    and the trapezoid's level weights w_l = 1, w_0 = w_Nt = 1/2 (dt cancels).  P is the orthogonal projection in the
+    discrete L2(Q) inner product of the cost and the Armijo distance (L2_norm_sq_Q), so P d is the steepest descent
+    direction among the piecewise-constant controls; and with a start control in that subspace every iterate
+    clip(c + s P d) stays in it bit for bit, so the sweeps, costs and trial kernels are the free loop's.  K = 1
+    (:meth:`stationary`) is a time-independent control: parameter identification, and the problem the default forward
+    sweeps of the PDE systems pose, which freeze the control at level 1.  K = num_steps + 1 (:meth:`identity`) is the
+    free space-time control.  The loops return the control as a full trajectory; :meth:`compact` gives its K fields."""
+
+    def __init__(self, num_steps, starts):
+        Nt = int(num_steps)
+        if Nt < 1:
+            raise ValueError(f"num_steps = {num_steps}: must be >= 1")
+        st = np.asarray(starts)
+        if st.ndim != 1 or st.size < 2:
+            raise ValueError("starts: K + 1 >= 2 interval boundaries are needed")
+        if not np.all(st == np.floor(st)):
+            raise ValueError("starts must be integers")
+        st = st.astype(np.int64)
+        if st[0] != 0 or st[-1] != Nt + 1:
+            raise ValueError(f"starts must begin at 0 and end at num_steps + 1 = {Nt + 1}")
+        if np.any(np.diff(st) <= 0):
+            raise ValueError("starts must be strictly increasing")
+        w = np.ones(Nt + 1)
+        w[0] = w[Nt] = 0.5
+        self.num_steps, self.K = Nt, st.size - 1
+        self.starts = st.astype(np.int32)
+        self.level_weights = w
+        self.interval_weights = np.add.reduceat(w, st[:-1])
+        self.interval_of_level = np.repeat(np.arange(self.K), np.diff(st))
+        for a in (self.starts, self.level_weights, self.interval_weights, self.interval_of_level):
+            a.setflags(write=False)
+
+    @classmethod
+    def stationary(cls, num_steps):
+        """One interval: a control that does not depend on time."""
+        return cls(num_steps, [0, int(num_steps) + 1])
+
+    @classmethod
+    def every(cls, num_steps, stride):
+        """Intervals of ``stride`` levels from level 0 on (the last one takes what is left)."""
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError(f"stride = {stride}: must be >= 1")
+        return cls(num_steps, list(range(0, int(num_steps) + 1, stride)) + [int(num_steps) + 1])
+
+    @classmethod
+    def identity(cls, num_steps):
+        """One interval per level: the free space-time control (the projection returns its input bit for bit)."""
+        return cls(num_steps, np.arange(int(num_steps) + 2))
+
+    def check(self, num_steps):
+        """Raises ValueError unless these intervals partition the levels of a problem of ``num_steps`` steps."""
+        if self.num_steps != int(num_steps):
+            raise ValueError(f"control intervals of {self.num_steps} steps for a problem of {num_steps}")
+        return self
+
+    def _levels(self, c, n):
+        c = np.asarray(c, dtype=np.float64)
+        if c.size != (self.num_steps + 1) * int(n):
+            raise ValueError(f"control of {c.size} values, expected (num_steps + 1) * n = {(self.num_steps + 1) * int(n)}")
+        return c.reshape(self.num_steps + 1, int(n))
+
+    def compact(self, c, n):
+        """The K fields of a control trajectory, a (K, n) array: ``restrict`` (for a control that is constant on the
+        intervals, its values there up to rounding; exactly so on an interval of one level)."""
+        x = self._levels(c, n) * self.level_weights[:, None]
+        return np.add.reduceat(x, self.starts[:-1].astype(np.int64), axis=0) / self.interval_weights[:, None]
+
+    def expand(self, ck):
+        """The (num_steps + 1) * n trajectory that holds the K fields ``ck`` (K, n) over their intervals."""
+        ck = np.asarray(ck, dtype=np.float64)
+        if ck.ndim != 2 or ck.shape[0] != self.K:
+            raise ValueError(f"fields of shape {ck.shape}, expected ({self.K}, n)")
+        return np.ascontiguousarray(ck[self.interval_of_level]).ravel()
+
+    def contains(self, c, n):
+        """True when the control trajectory ``c`` is constant on every interval, exactly."""
+        x = self._levels(c, n)
+        return bool(np.array_equal(x, x[self.starts[:-1].astype(np.int64)][self.interval_of_level]))
+
+    def need(self, c, n, num_steps):
+        """The loops' entry check: the intervals fit the problem and the start control ``c`` lies in the subspace."""
+        self.check(num_steps)
+        if not self.contains(c, n):
+            raise ValueError("c0 is not constant in time on the control intervals (control_time): project it first, e.g. "
+                             "control_time.expand(control_time.compact(c0, n))")
+        return self
+
+
 class SolidBodyDrift:
     """Drift-control advection problem on one GPU; ``batch`` independent trajectories advance
     together in every kernel launch (Armijo trial steps, regularisation sweeps)."""
@@ -179,18 +277,40 @@ class SolidBodyDrift:
         self.ctx.solidbody_adjoint(self.Arot, c, u, uhat, p, self.num_steps, self.dt, self.eps, self.rot_scale,
                                    self.drift, optim == "alltime", self.batch if batch is None else batch, c_shared)
 
-    def descent_direction(self, c, u, p, beta, d, scratch=None):
+    def descent_direction(self, c, u, p, beta, d, scratch=None, control_time=None):
         """d_k = ChebSI(-(beta*M*c_k + int p_k (b.grad u_k) v)) for every level k (finaltime.py:228-238);
-        all levels are one batched launch sequence."""
+        all levels are one batched launch sequence.  ``control_time`` (a :class:`ControlIntervals`): the direction
+        projected onto the controls constant on its K intervals.  The projection commutes with the per-level mass solve,
+        so the right-hand sides are restricted first and K systems are solved in place of num_steps + 1."""
         levels = self.num_steps + 1
         own = scratch is None
         rhs = self.ctx.empty(self.tlen) if own else scratch
         try:
             self.ctx.drift_gradient_rhs(c, u, p, beta, rhs, levels, self.drift)
-            self.ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=levels)
+            if control_time is None:
+                self.ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=levels)
+            else:
+                self._projected_solve(control_time, rhs, d, 1)
         finally:
             if own:
                 rhs.free()
+
+    def _projected_solve(self, ct, rhs, d, batch):
+        """d[b] = prolong(ChebSI(restrict(rhs[b]))) for ``batch`` trajectories: batch * K mass solves in one sequence."""
+        K, n = ct.check(self.num_steps).K, self.n
+        rk, dk = self._interval_fields(2 * batch * K * n)
+        self.ctx.time_restrict(rhs, ct.starts, self.num_steps, rk, batch)
+        self.ctx.chebsi(rk, dk, 20, 0.5, 2.0, batch=batch * K)
+        self.ctx.time_prolong(dk, ct.starts, self.num_steps, d, batch)
+
+    def _interval_fields(self, count):
+        """two device buffers of count / 2 doubles each for the K fields of a projection (kept, grown on demand)"""
+        buf = self.__dict__.get("_ivl_buf")
+        if buf is None or buf.count < count:
+            if buf is not None:
+                buf.free()
+            buf = self.__dict__["_ivl_buf"] = self.ctx.empty(count)
+        return buf.ptr, buf.ptr + 8 * (count // 2)
 
     def cost(self, u, target, c, beta, optim, batch=None, obs=None):
         if _need_obs(optim, obs):       # every member (all Armijo trials of a batched sweep) in one call
@@ -264,9 +384,13 @@ class LinearSourceControl(SolidBodyDrift):
         """:259-274 (all-time) / advection_FCT_PDECO_finaltime.py (final-time)"""
         self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True, obs=obs)
 
-    def descent_direction(self, c, p, beta, d):
-        """advection_FCT_PDECO_alltime_exact.py:278: d = -(beta*c - p), every level, the script's operation order."""
+    def descent_direction(self, c, p, beta, d, control_time=None):
+        """advection_FCT_PDECO_alltime_exact.py:278: d = -(beta*c - p), every level, the script's operation order.
+        ``control_time`` (a :class:`ControlIntervals`): then projected onto the controls constant on its intervals."""
         self.ctx.descent_pointwise(self.tlen, beta, c, p, d)
+        if control_time is not None:
+            K = control_time.check(self.num_steps).K
+            self.ctx.time_project(d, control_time.starts, self.num_steps, self._interval_fields(2 * K * self.n)[0])
 
     def sensitivity(self, d, w):
         """:282-297: w = S(d), the state sweep with source d and a zero initial condition (level 0 of ``w`` is zeroed)."""
@@ -380,30 +504,31 @@ def finaltime_exact_fields(t, X, Y, T=0.1, beta=0.1, c_lower=0.0, c_upper=1.0, e
 
 
 def pgd_solidbody_finaltime(prob: SolidBodyDrift, u0, uhat_T, c0, beta, c_lower, c_upper, iters,
-                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None):
+                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None):
     """Final-time variant of :func:`pgd_solidbody` (advection_solidbody_FCT_PDECO_finaltime_Garvie.py)."""
     return pgd_solidbody(prob, u0, uhat_T, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="finaltime")
+                         optim="finaltime", control_time=control_time)
 
 
 def pgd_solidbody_alltime(prob: SolidBodyDrift, u0, uhat_all, c0, beta, c_lower, c_upper, iters,
-                          gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None):
+                          gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None):
     """All-time variant (advection_solidbody_FCT_PDECO_alltime_Garvie.py, config C5's loop): ``uhat_all``
     is the target trajectory ((Nt+1)*n, level 0 = u0)."""
     return pgd_solidbody(prob, u0, uhat_all, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="alltime")
+                         optim="alltime", control_time=control_time)
 
 
 def pgd_solidbody_snapshots(prob: SolidBodyDrift, u0, uhat, obs: Observations, c0, beta, c_lower, c_upper, iters,
-                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None):
+                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None):
     """Snapshot variant of :func:`pgd_solidbody`: ``uhat`` is a (num_steps+1)*n trajectory of which only the levels that
     ``obs`` observes are read (the others may hold anything, NaN included)."""
     return pgd_solidbody(prob, u0, uhat, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="snapshots", obs=obs)
+                         optim="snapshots", obs=obs, control_time=control_time)
 
 
 def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters,
-                  gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None):
+                  gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None,
+                  control_time=None):
     """Projected gradient descent for the drift-control problem, following the loop of
     advection_solidbody_FCT_PDECO_finaltime_Garvie.py:164-330 / ..._alltime_Garvie.py:164-340 step for step:
 
@@ -420,10 +545,14 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     the same computation; the states agree to the low-order solver tolerance, 1e-13).
     optim="snapshots": target trajectory read at the levels of ``obs`` only, the adjoint and cost of
     :class:`Observations`; u is seeded with the target at the observed levels (both modes above, seen as observations).
+    ``control_time`` (a :class:`ControlIntervals`): the control is constant in time on its intervals; d is projected onto
+    these controls and ``c0`` must be one of them (ValueError otherwise).  None: the free space-time control.
     Returns ``(u, p, c, history)`` as NumPy arrays + a dict of per-iteration scalars."""
     snap = _need_obs(optim, obs)
     alltime = optim == "alltime" or snap         # (the target is a trajectory)
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    if control_time is not None:
+        control_time.need(c0, n, Nt)
     B = int(max_armijo) if speculative else 1
     u = ctx.zeros(tl)
     u.upload(np.concatenate([np.asarray(u0, dtype=np.float64), np.zeros(tl - n)]))
@@ -454,7 +583,10 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     try:
         for it in range(iters):
             prob.adjoint(c_prev, u, uh, p, optim, batch=1, obs=obs)
-            prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs)
+            if control_time is None:
+                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs)
+            else:
+                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, control_time=control_time)
             ctx.project_control(c_prev, s0, d, c_lower, c_upper, c, tl)
             prob.forward(c, u, batch=1)
             J_k = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs)[0])
@@ -512,7 +644,7 @@ class LockstepResult(list):
 
 
 def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c_upper, iters,
-                           gam=1e-4, s0=1.0, max_armijo=10, tol=None, optim="finaltime"):
+                           gam=1e-4, s0=1.0, max_armijo=10, tol=None, optim="finaltime", control_time=None):
     """P projected-gradient loops of :func:`pgd_solidbody` (speculative form) carried in lockstep: problem p has the
     regularisation ``betas[p]`` and, optionally, its own start control (``c0`` of shape (P, tlen); one (tlen,) control is
     shared), first step length (``s0``: a scalar or P values) and target (``uhat``: one target or P).  The regularisation
@@ -524,6 +656,8 @@ def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c
     the Armijo decisions from the 2 * P_active * max_armijo scalars.  A batch member computes what it would compute alone,
     so every problem follows its own pgd_solidbody run (to the low-order solver tolerance; P = 1 is that run, bit for bit).
     A problem whose rel_change < ``tol`` is finished: its results are kept and it leaves all later launches.
+    ``control_time`` (a :class:`ControlIntervals`): as in pgd_solidbody, for every problem; the directions of the active
+    problems are K * P_active mass solves in one sequence.
     Returns a :class:`LockstepResult`; each ``hist`` has pgd_solidbody's keys."""
     if optim == "snapshots":
         raise ValueError("optim='snapshots' is not yet carried by the lockstep loop (the snapshot cost takes one target per "
@@ -546,6 +680,9 @@ def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c
         c0 = np.broadcast_to(c0, (P, tl))
     elif c0.shape != (P, tl):
         raise ValueError(f"c0 of shape {c0.shape}, expected ({tl},) or ({P}, {tl})")
+    if control_time is not None:
+        for c0p in c0:
+            control_time.need(c0p, n, Nt)
     s0 = np.asarray(s0, dtype=np.float64)
     if s0.ndim == 0:
         s0 = np.full(P, float(s0))
@@ -614,7 +751,10 @@ def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c
             for j in range(Pa):
                 ctx.drift_gradient_rhs(at(c_prev, j * tl), at(u, j * tl), at(p, j * tl), b_act[j], at(rhs, j * tl), Nt + 1,
                                        prob.drift)
-            ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=(Nt + 1) * Pa)
+            if control_time is None:
+                ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=(Nt + 1) * Pa)
+            else:
+                prob._projected_solve(control_time, rhs, d, Pa)
             ctx.trial_controls(c_prev, d, s_act, Pa, 1, c_lower, c_upper, tl, c)
             prob.forward(c, u, batch=Pa)
             J_k, _ = ctx.member_costs(u, uhP, c, b_act, Pa, 1, Nt, dt, optim,
@@ -665,7 +805,8 @@ def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c
 
 
 def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
-                       increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None):
+                       increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
+                       control_time=None):
     """Projected gradient descent for the linear source-control problem, the loop of
     advection_FCT_PDECO_alltime_exact.py:212-330 (optim="alltime", stop="both") and advection_FCT_PDECO_finaltime.py:
     170-280 (optim="finaltime", stop="cost"):
@@ -683,6 +824,8 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
 
     optim="snapshots" (increment="resolve" only): the adjoint and cost of ``obs``, an :class:`Observations`; ``uhat`` is
     a trajectory read at the observed levels only.
+    ``control_time`` (a :class:`ControlIntervals`): the control is constant in time on its intervals; d is projected onto
+    these controls (both increments: in linear mode the sensitivity is S(P d)) and ``c0`` must be one of them.
     ``uhat``: target trajectory (all-time) or uhat_T (final-time, n values); ``g``: fixed source trajectory or None.
     Everything stays in HBM; the host sees scalars only.  Returns ``(u, p, c, hist)`` like the scripts: u and p are the
     last iteration's state and adjoint (at the control that iteration started from), c the last accepted control.
@@ -713,6 +856,8 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
     u0 = np.asarray(u0, dtype=np.float64).ravel()
     if u0.size != n:
         raise ValueError(f"u0 of {u0.size} values, expected {n}")
+    if control_time is not None:
+        control_time.need(c0, n, Nt)
     bufs = []
 
     def alloc(count, zero=True):
@@ -746,7 +891,10 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             prob.state(src, u, batch=1)
             hist["cost_state"].append(cost(u, c))
             prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs) if snap else prob.adjoint_state(u, uh, p, optim, batch=1)
-            prob.descent_direction(c, p, beta, d)
+            if control_time is None:
+                prob.descent_direction(c, p, beta, d)
+            else:
+                prob.descent_direction(c, p, beta, d, control_time=control_time)
             if linear:
                 prob.sensitivity(d, w)
                 J, dist = ctx.linear_trial_costs(u, w, uh, c, d, s0, K, c_lower, c_upper, beta, Nt, dt, optim)

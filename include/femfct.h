@@ -346,6 +346,23 @@ int femfct_member_costs(femfct_ctx* ctx, const double* u_traj, const double* uha
                         const double* c_traj, const double* cref, const double* beta_host, int32_t P, int32_t K,
                         int32_t num_steps, double dt, int32_t finaltime, double* J_host, double* dist_host);
 
+/* Controls that are piecewise constant in time: K intervals of time levels, interval k = the levels
+ * starts_host[k] <= l < starts_host[k+1] (K + 1 strictly increasing values, starts_host[0] = 0, starts_host[K] =
+ * num_steps + 1; anything else is FEMFCT_ERR_INVALID).  With the trapezoid's level weights w_l of L2_norm_sq_Q (1, and
+ * 1/2 at levels 0 and num_steps) and W_k = sum_{l in k} w_l,
+ *   restrict:  out_dev[(b*K + k)*n + i] = (sum_{l in k} w_l x_traj[(b*(num_steps+1) + l)*n + i]) / W_k
+ *   prolong:   out_traj[(b*(num_steps+1) + l)*n + i] = y_dev[(b*K + k(l))*n + i]
+ * for the batch members b < batch.  prolong(restrict(.)) is the orthogonal projection, in the inner product of
+ * femfct_l2_norm_sq_Q, onto the trajectories that are constant on every interval; an interval of one level returns that
+ * level exactly.  The sums run in a fixed order that depends on an interval's length alone (no atomics): the same bits
+ * for every batch size, member and run.  starts_host is read before the call returns.  One launch sequence per call, does
+ * not synchronise.  out_dev / out_traj must not alias the call's input; the x_traj of a restrict and the out_traj of the
+ * prolong that follows may be one buffer (the projection in place). */
+int femfct_time_restrict(femfct_ctx* ctx, const double* x_traj, const int32_t* starts_host, int32_t K, int32_t num_steps,
+                         int32_t batch, double* out_dev);
+int femfct_time_prolong(femfct_ctx* ctx, const double* y_dev, const int32_t* starts_host, int32_t K, int32_t num_steps,
+                        int32_t batch, double* out_traj);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
