@@ -22,6 +22,7 @@ REGIME_ROWS, REGIME_STRIPS, REGIME_TILE32, REGIME_PATCH64, REGIME_MESH = 0, 1, 2
 ABI_VERSION = 5
 MAX_TRIALS = 16          # FEMFCT_MAX_TRIALS: Armijo trials per femfct_linear_trial_costs / femfct_source_trials call
 MAX_MEMBERS = 256        # FEMFCT_MAX_MEMBERS: problems x trials per femfct_trial_controls / femfct_member_costs call
+MAX_GRAM_FIELDS = 17     # FEMFCT_MAX_GRAM_FIELDS: trajectories per femfct_q_gram / femfct_q_combine call (a memory of 8)
 
 
 class FemFctError(RuntimeError):
@@ -158,6 +159,9 @@ SIGNATURES = {
     "femfct_member_costs": (C.c_int, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _d, _i, _p, _p]),
     "femfct_time_restrict": (C.c_int, [_p, _p, _p, _i, _i, _i, _p]),
     "femfct_time_prolong": (C.c_int, [_p, _p, _p, _i, _i, _i, _p]),
+    "femfct_free_set": (C.c_int, [_p, _p, _p, _d, _d, C.c_int64, _p]),
+    "femfct_q_gram": (C.c_int, [_p, _p, _i, _p, _i, _d, _p]),
+    "femfct_q_combine": (C.c_int, [_p, _p, _p, _i, _p, _p, _d, C.c_int64, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

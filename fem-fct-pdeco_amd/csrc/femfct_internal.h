@@ -267,6 +267,8 @@ int femfct_round_budget(const femfct_ctx* ctx, int b);
 FEMFCT_INTERNAL void femfct_forget_jacobi_budgets(femfct_ctx* ctx);       // femfct_set_solver, femfct_set_fusion
 FEMFCT_INTERNAL void femfct_forget_bicgstab_handovers(femfct_ctx* ctx);   // femfct_set_solver
 FEMFCT_INTERNAL void femfct_forget_cheb_off(femfct_ctx* ctx);             // femfct_set_species_solver
+// the reductions' scratch (ctx->d_scratch, kernels_pgd.hip) holds at least `doubles` values; growing it discards its contents
+FEMFCT_INTERNAL int femfct_ensure_scratch(femfct_ctx* ctx, size_t doubles);
 
 // graph-key helpers
 static inline uint64_t key_bits(const void* p) { return (uint64_t)(uintptr_t)p; }

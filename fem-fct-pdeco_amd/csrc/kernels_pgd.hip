@@ -337,6 +337,8 @@ int enqueue_norm(femfct_ctx* ctx, const double* a, const double* b, int64_t a_ls
 
 }  // namespace
 
+int femfct_ensure_scratch(femfct_ctx* ctx, size_t doubles) { return ensure_scratch(ctx, doubles); }
+
 extern "C" {
 
 int femfct_l2_norm_sq_Q(femfct_ctx* ctx, const double* a_dev, const double* b_dev, int32_t num_steps, double dt,

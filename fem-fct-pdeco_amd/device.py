@@ -517,6 +517,39 @@ class Context:
         self.time_restrict(x, starts, num_steps, scratch, batch)
         self.time_prolong(scratch, starts, num_steps, x, batch)
 
+    # -- limited-memory quasi-Newton primitives (solvers.LimitedMemory) -----------------------
+    @staticmethod
+    def _fields(fields):
+        J = len(fields)
+        if not 1 <= J <= _lib.MAX_GRAM_FIELDS:
+            raise ValueError(f"{J} fields: must be in 1..{_lib.MAX_GRAM_FIELDS}")
+        return (C.c_void_p * J)(*[dptr(f) for f in fields]), J
+
+    def free_set(self, c, g, c_lower, c_upper, count, mask):
+        """mask[k] = 0 where the value is bound ((c <= c_lower and g > 0) or (c >= c_upper and g < 0)), else 1: ``count``
+        bytes on the device (any device buffer of at least that size).  One launch, does not synchronise."""
+        check(self.handle, lib.femfct_free_set(self.handle, dptr(c), dptr(g), float(c_lower), float(c_upper), int(count),
+                                               dptr(mask)))
+
+    def q_gram(self, fields, num_steps, dt, mask=None) -> np.ndarray:
+        """The (J, J) Gram matrix of the trajectories ``fields`` in the L2(Q) inner product of ``l2_norm_sq_Q``, each
+        masked to the free set ``mask`` (bytes as ``free_set`` writes them; None: all free).  Exactly symmetric, the same
+        bits on every call; without a mask the diagonal is ``l2_norm_sq_Q`` bit for bit."""
+        ptrs, J = self._fields(fields)
+        G = np.empty((J, J))
+        check(self.handle, lib.femfct_q_gram(self.handle, ptrs, J, dptr(mask), int(num_steps), float(dt), _host_ptr(G)))
+        return G
+
+    def q_combine(self, fields, coef, count, out, mask=None, fallback=None, fallback_scale=0.0):
+        """out = ((coef[0]*fields[0] + coef[1]*fields[1]) + ...) where ``mask`` is set (None: everywhere), and
+        fallback_scale * fallback elsewhere; bitwise the NumPy expression.  ``out`` must not be an input."""
+        ptrs, J = self._fields(fields)
+        cf = _as_f64(coef).reshape(-1)
+        if cf.size != J:
+            raise ValueError(f"q_combine: {cf.size} coefficients for {J} fields")
+        check(self.handle, lib.femfct_q_combine(self.handle, ptrs, _host_ptr(cf), J, dptr(mask), dptr(fallback),
+                                                float(fallback_scale), int(count), dptr(out)))
+
     # -- non-FCT species / PDE systems ---------------------------------------------------
     def descent_pointwise(self, count, beta, c, x, out, y=None, scale=1.0, divisor=1.0):
         """out = -(beta*c - t), t = x*y/divisor (y given) or scale*x"""

@@ -956,3 +956,359 @@ def source_control_errors(mesh: SquareMeshP1, u, c, p, exact, dx, dt, iterations
     vals = [out["rel_u"], out["rel_c"], out["rel_p"], out["werr_u"], out["werr_c"], out["werr_p"]]
     out["csv"] = " , ".join(str(float(v)) for v in vals) + f" , {int(iterations)}"
     return out
+
+
+# ---------------------------------------------------------------------------------------------- projected L-BFGS
+# An extension (no reference call): the loops above are steepest descent in the L2(Q) metric; these keep their sweeps,
+# costs and Armijo test and replace the direction by a limited-memory quasi-Newton one on the free set of the box.
+def two_loop_coefficients(G, k):
+    """The L-BFGS two-loop recursion on coefficient vectors over F = [s_1..s_k, y_1..y_k, g] (oldest pair first), every
+    inner product read from the Gram matrix ``G`` of F: pair i takes part iff G[s_i, y_i] > 0, rho_i = 1 / G[s_i, y_i],
+    and the initial scaling is gamma = G[s, y] / G[y, y] of the newest pair that takes part (1 if none does).  Returns
+    ``(r, pairs that took part)`` with H g = F r."""
+    J = 2 * k + 1
+    q = np.zeros(J)
+    q[2 * k] = 1.0
+    part = [i for i in range(k) if G[i, k + i] > 0]
+    alpha = {}
+    for i in reversed(part):
+        alpha[i] = (G[i] @ q) / G[i, k + i]
+        q[k + i] -= alpha[i]
+    gamma = G[part[-1], k + part[-1]] / G[k + part[-1], k + part[-1]] if part else 1.0
+    r = gamma * q
+    for i in part:
+        b = (G[k + i] @ r) / G[i, k + i]
+        r[i] += alpha[i] - b
+    return r, len(part)
+
+
+class LimitedMemory:
+    """A ring of up to ``memory`` pairs of device trajectories s_i = c_{k+1} - c_k, y_i = g_{k+1} - g_k (``tl`` doubles
+    each; g the L2(Q) Riesz representative of the gradient) and the quasi-Newton direction they give for a control with
+    box constraints.  A pair is stored only if, unmasked, <s, y>_Q > 1e-10 sqrt(<s, s>_Q <y, y>_Q).
+
+    :meth:`direction` is three launches and one read-back of J*J doubles, J = 2 pairs + 1, whatever the memory: the free
+    set (``Context.free_set``), the Gram matrix of F = [s.., y.., g] masked to it (``Context.q_gram``), the two-loop
+    recursion on the host in coefficient space (:func:`two_loop_coefficients`) and one combination of F
+    (``Context.q_combine``): -H g on the free set, -g on the bound set.  The mask's bytes are read back as well, for
+    ``free_fraction``.  ``dt`` scales the inner product (the direction does not depend on it).  :meth:`close` frees the
+    ring."""
+    PAIR_TOL = 1e-10
+
+    def __init__(self, ctx: Context, tl: int, memory: int, dt: float = 1.0):
+        self.ctx, self.tl, self.memory, self.dt = ctx, int(tl), int(memory), float(dt)
+        if not 0 <= self.memory <= (_lib.MAX_GRAM_FIELDS - 1) // 2:
+            raise ValueError(f"memory = {memory}: must be in 0..{(_lib.MAX_GRAM_FIELDS - 1) // 2}")
+        if ctx.n < 1 or self.tl % ctx.n:
+            raise ValueError(f"tl = {tl}: must be (num_steps + 1) * n with n = {ctx.n}")
+        self.num_steps = self.tl // ctx.n - 1
+        # memory + 1 slots: a candidate pair is formed in the spare one and takes the oldest pair's place only if stored
+        self._slots = [(ctx.empty(self.tl), ctx.empty(self.tl)) for _ in range(self.memory + 1 if self.memory else 0)]
+        self._ring = []                 # slot indices, oldest first
+        self._mask = ctx.empty((self.tl + 7) // 8)      # tl bytes
+        self.free_fraction = 1.0
+
+    @property
+    def pairs(self):
+        return len(self._ring)
+
+    def drop(self):
+        self._ring = []
+
+    def push(self, c, c_old, g, g_old) -> bool:
+        """Forms s = c - c_old, y = g - g_old and stores the pair if it passes the curvature test."""
+        if not self.memory:
+            return False
+        spare = next(i for i in range(self.memory + 1) if i not in self._ring)
+        s, y = self._slots[spare]
+        self.ctx.axpby(self.tl, 1.0, c, -1.0, c_old, s)
+        self.ctx.axpby(self.tl, 1.0, g, -1.0, g_old, y)
+        G = self.ctx.q_gram([s, y], self.num_steps, self.dt)
+        if not G[0, 1] > self.PAIR_TOL * np.sqrt(G[0, 0] * G[1, 1]):
+            return False
+        self._ring.append(spare)
+        if len(self._ring) > self.memory:
+            del self._ring[0]
+        return True
+
+    def direction(self, c, g, c_lower, c_upper, out) -> str:
+        """out = the direction at the control ``c`` with gradient ``g``; returns "qn" when pairs took part, else "g"
+        (out = -g).  If the quasi-Newton direction is not a descent direction on the free set the ring is dropped and
+        out = -g.  ``free_fraction`` is then the share of free values."""
+        ctx, tl, k = self.ctx, self.tl, len(self._ring)
+        ctx.free_set(c, g, c_lower, c_upper, tl, self._mask)
+        F = [self._slots[i][0] for i in self._ring] + [self._slots[i][1] for i in self._ring] + [g]
+        G = ctx.q_gram(F, self.num_steps, self.dt, mask=self._mask)
+        r, took = two_loop_coefficients(G, k)
+        m = np.empty(tl, dtype=np.uint8)
+        _lib.check(ctx.handle, _lib.lib.femfct_memcpy_d2h(ctx.handle, m.ctypes.data, dptr(self._mask), tl))
+        self.free_fraction = float(m.mean())
+        if not r @ G[:, -1] > 0:
+            self.drop()
+            ctx.q_combine([g], [-1.0], tl, out)
+            return "g"
+        ctx.q_combine(F, -r, tl, out, mask=self._mask, fallback=g, fallback_scale=-1.0)
+        return "qn" if took else "g"
+
+    def close(self):
+        for s, y in self._slots:
+            s.free()
+            y.free()
+        self._slots, self._ring = [], []
+        self._mask.free()
+
+
+def _lbfgs_iterate(ctx, lm, tl, c, g, bufs, J0, gradient, search, take, c_lower, c_upper, max_iters, gam, s0, K, stop):
+    """The iteration both L-BFGS loops share.  ``gradient()`` fills g at the current (c, u); ``search(dir, J, svals,
+    margins)`` looks at the trials c_t = clip(c + s_t dir) in order and returns ``(t, J_t, ||c_t - c||^2_Q, trials
+    looked at)`` of the first that passes the Armijo test (t None: none did); ``take(t)`` makes trial t the iterate;
+    ``stop(J, J_t, dist)`` ends the loop after an accepted step."""
+    dirv, c_old, g_old = bufs
+    hist = dict(cost=[], armijo_k=[], step=[], rel_change=[], armijo_margin=[], used=[], pairs=[], free_fraction=[],
+                sweeps=[], wall=[], wall0=time.perf_counter(), cost0=J0, stalled=False)
+    svals = [s0 * (1 / 2 ** k) for k in range(K)]
+    J, sweeps, have_old = J0, 1, False
+    for _ in range(max_iters):
+        gradient()
+        sweeps += 1
+        if have_old:
+            lm.push(c, c_old, g, g_old)
+        used = lm.direction(c, g, c_lower, c_upper, dirv)
+        pairs, free = lm.pairs, lm.free_fraction
+        margins = []
+        while True:
+            t, Jt, dist, looked = search(dirv, J, svals, margins)
+            sweeps += looked
+            if t is not None or used != "qn":
+                break
+            lm.drop()                               # no quasi-Newton trial passed: -g within the same iteration
+            ctx.q_combine([g], [-1.0], tl, dirv)
+            used = "g"
+        if t is None:
+            hist["stalled"] = True
+            break
+        c_old.copy_from(c, tl)
+        g_old.copy_from(g, tl)
+        have_old = True
+        take(t)
+        for key, v in (("cost", Jt), ("armijo_k", t + 1), ("step", svals[t]), ("rel_change", abs(J - Jt) / abs(J)),
+                       ("armijo_margin", margins), ("used", used), ("pairs", pairs), ("free_fraction", free),
+                       ("sweeps", sweeps), ("wall", time.perf_counter())):
+            hist[key].append(v)
+        ended = stop(J, Jt, dist)
+        J = Jt
+        if ended:
+            break
+    hist["iterations"] = len(hist["cost"])
+    hist["armijo_margin_min"] = min((abs(m) for ms in hist["armijo_margin"] for m in ms), default=None)
+    return hist
+
+
+def _first_accepted(J, dist, J_k, svals, gam, margins):
+    """the first trial with J_t - J_k <= -gam/s_t dist_t among the evaluated ones: (t or None, trials looked at)"""
+    for t, s in enumerate(svals[:len(J)]):
+        margins.append((float(J[t]) - J_k + gam / s * float(dist[t])) / abs(J_k))
+        if J[t] - J_k <= -gam / s * dist[t]:
+            return t, t + 1
+    return None, len(J)
+
+
+def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters, memory=5, gam=1e-4, s0=1.0,
+                    max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None, control_time=None):
+    """Projected L-BFGS descent for the drift-control problem: the sweeps, cost, direction kernels and Armijo test of
+    :func:`pgd_solidbody` with the direction of a :class:`LimitedMemory` of ``memory`` pairs.  Per iteration, at the
+    control c with u = S(c) and J = J(u, c):
+
+        adjoint(c, u) -> g = -descent_direction (projected with ``control_time``) -> push the pair of the previous
+        accepted step -> dir -> trials c_t = clip(c + s0/2^t dir): accept the first with
+        J(c_t) - J <= -gam/s_t ||c_t - c||^2_Q
+
+    If no quasi-Newton trial is accepted the ring is dropped and -g is searched within the same iteration; if that
+    fails too the loop stops with ``history["stalled"] = True``.  There is no unconditional first step (this is a new
+    loop, not a restatement of a script), so an accepted cost never exceeds the previous one.  ``memory=0`` is plain
+    projected gradient with this search.  ``speculative=True`` evaluates the ``max_armijo`` trials as one batch, as
+    pgd_solidbody does.  With ``control_time`` s, y, g and the free set are constant on every interval, so the iterates
+    stay piecewise constant bit for bit.  ``optim``, ``obs``, ``tol``: as in pgd_solidbody.
+
+    Returns ``(u, p, c, history)``; history: ``cost``, ``armijo_k``, ``armijo_margin`` (every trial looked at, the
+    quasi-Newton ones first), ``used`` ("qn" / "g"), ``pairs``, ``free_fraction``, ``sweeps`` (state and adjoint sweeps so
+    far, counting the trials a sequential search looks at), ``step``, ``rel_change``, ``wall``, ``cost0``, ``stalled``."""
+    snap = _need_obs(optim, obs)
+    alltime = optim == "alltime" or snap
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    K = int(max_armijo)
+    if K < 1:
+        raise ValueError(f"max_armijo = {max_armijo}: must be >= 1")
+    u0 = np.asarray(u0, dtype=np.float64).ravel()
+    if u0.size != n:
+        raise ValueError(f"u0 of {u0.size} values, expected {n}")
+    c0 = np.asarray(c0, dtype=np.float64).ravel()
+    if c0.size != tl:
+        raise ValueError(f"c0 of {c0.size} values, expected {tl}")
+    uhat = np.asarray(uhat, dtype=np.float64).ravel()
+    if uhat.size != (tl if alltime else n):
+        raise ValueError(f"target of {uhat.size} values, expected {tl if alltime else n} for optim='{optim}'")
+    if control_time is not None:
+        control_time.need(c0, n, Nt)
+    B = K if speculative else 1
+    lm = LimitedMemory(ctx, tl, memory, dt)
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    try:
+        u, p, d, g, rhs = alloc(tl), alloc(tl), alloc(tl), alloc(tl), alloc(tl, False)
+        c = alloc(tl, False).upload(c0)
+        qn_bufs = (alloc(tl, False), alloc(tl, False), alloc(tl, False))
+        uh = alloc(uhat.size, False).upload(uhat)
+        uhB = alloc(B * uhat.size, False)
+        cB, uB, ckB = alloc(B * tl), alloc(B * tl), alloc(B * tl, False)
+        u0d = alloc(n, False).upload(u0)
+        u.copy_from(u0d, n)
+        for k in range(B):
+            uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
+            uB.copy_from(u0d, n, dst_off=k * tl)          # level 0 of every trial trajectory = the initial condition
+        cost = lambda uu, hh, cc, b: prob.cost(uu, hh, cc, beta, optim, batch=b, obs=obs)
+        prob.forward(c, u, batch=1)
+        J0 = float(cost(u, uh, c, 1)[0])
+
+        def gradient():
+            prob.adjoint(c, u, uh, p, optim, batch=1, obs=obs)
+            if control_time is None:
+                prob.descent_direction(c, u, p, beta, d, scratch=rhs)
+            else:
+                prob.descent_direction(c, u, p, beta, d, scratch=rhs, control_time=control_time)
+            ctx.axpby(tl, -1.0, d, 0.0, None, g)
+
+        def search(dirv, J_k, svals, margins):
+            if speculative:
+                for k, s in enumerate(svals):
+                    ctx.project_control(c, s, dirv, c_lower, c_upper, cB.ptr + 8 * k * tl, tl)
+                    ckB.copy_from(c, tl, dst_off=k * tl)
+                prob.forward(cB, uB, batch=B)
+                J = cost(uB, uhB, cB, B)
+                dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=B)
+                t, looked = _first_accepted(J, dist, J_k, svals, gam, margins)
+                return t, (None if t is None else float(J[t])), (None if t is None else float(dist[t])), looked
+            for k, s in enumerate(svals):
+                ctx.project_control(c, s, dirv, c_lower, c_upper, cB, tl)
+                prob.forward(cB, uB, batch=1)
+                J = cost(uB, uh, cB, 1)
+                dist = ctx.l2_norm_sq_Q(cB, c, Nt, dt)
+                t, _ = _first_accepted(J, dist, J_k, [s], gam, margins)
+                if t is not None:
+                    return k, float(J[0]), float(dist[0]), k + 1
+            return None, None, None, len(svals)
+
+        def take(t):
+            off = t * tl if speculative else 0
+            c.copy_from(cB, tl, src_off=off)
+            u.copy_from(uB, tl, src_off=off)
+
+        stop = lambda J, Jt, dist: tol is not None and abs(J - Jt) / abs(J) < tol
+        hist = _lbfgs_iterate(ctx, lm, tl, c, g, qn_bufs, J0, gradient, search, take, c_lower, c_upper, int(iters), gam,
+                              s0, K, stop)
+        return u.download(), p.download(), c.download(), hist
+    finally:
+        lm.close()
+        for a in bufs:
+            a.free()
+
+
+def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
+                         memory=5, gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
+                         control_time=None):
+    """Projected L-BFGS descent for the linear source-control problem (:class:`LinearSourceControl`,
+    :class:`LinearReactionSourceControl`): the iteration of :func:`lbfgs_solidbody` with the gradient
+    -descent_direction = beta c - p, the trial controls and sources of ``femfct_source_trials`` and the ``max_armijo``
+    trial states as one batched sweep, as ``pgd_source_control(increment="resolve")`` runs them.  The Armijo test
+    compares with the cost of the current iterate, J(S(g + c_k), c_k) (no unconditional first step and no 10 J start
+    value).  The loop runs while stop_crit2 = |J_k - J_acc| / |J_k| >= tol, or (stop="both")
+    stop_crit = ||c_{k+1} - c_k||^2_Q / ||c_k||^2_Q >= tol, and fewer than ``max_iters`` iterations have run.
+    Arguments and return value as pgd_source_control; the history is lbfgs_solidbody's with ``stop_crit``, ``stop_crit2``."""
+    snap = _need_obs(optim, obs)
+    if stop not in ("both", "cost"):
+        raise ValueError(f"Invalid value for 'stop': '{stop}'. Must be one of ['both', 'cost'].")
+    K = int(max_armijo)
+    if not 1 <= K <= _lib.MAX_TRIALS:
+        raise ValueError(f"max_armijo = {K}: must be in 1..{_lib.MAX_TRIALS}")
+    alltime = optim == "alltime" or snap
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    uhat = np.asarray(uhat, dtype=np.float64).ravel()
+    if uhat.size != (tl if alltime else n):
+        raise ValueError(f"target of {uhat.size} values, expected {tl if alltime else n} for optim='{optim}'")
+    c0 = np.asarray(c0, dtype=np.float64).ravel()
+    if c0.size != tl:
+        raise ValueError(f"c0 of {c0.size} values, expected {tl}")
+    if g is not None and np.asarray(g).size != tl:
+        raise ValueError(f"g of {np.asarray(g).size} values, expected {tl}")
+    u0 = np.asarray(u0, dtype=np.float64).ravel()
+    if u0.size != n:
+        raise ValueError(f"u0 of {u0.size} values, expected {n}")
+    if control_time is not None:
+        control_time.need(c0, n, Nt)
+    lm = LimitedMemory(ctx, tl, memory, dt)
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    try:
+        u, p, d, gr, c = alloc(tl), alloc(tl), alloc(tl), alloc(tl), alloc(tl, False).upload(c0)
+        u.upload(np.concatenate([u0, np.zeros(tl - n)]))
+        qn_bufs = (alloc(tl, False), alloc(tl, False), alloc(tl, False))
+        uh = alloc(uhat.size, False).upload(uhat)
+        gd = None if g is None else alloc(tl, False).upload(g)
+        src = c if gd is None else alloc(tl, False)
+        cB, uB, ckB, uhB = alloc(K * tl, False), alloc(K * tl), alloc(K * tl, False), alloc(K * uhat.size, False)
+        srcB = cB if gd is None else alloc(K * tl, False)
+        for k in range(K):
+            uB.copy_from(u, n, dst_off=k * tl)              # level 0 of every trial state = u0
+            uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
+        if gd is not None:
+            ctx.axpby(tl, 1.0, gd, 1.0, c, src)
+        prob.state(src, u, batch=1)
+        J0 = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs)[0])
+        crit = dict(stop_crit=[], stop_crit2=[])
+
+        def gradient():
+            prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs) if snap else prob.adjoint_state(u, uh, p, optim, batch=1)
+            if control_time is None:
+                prob.descent_direction(c, p, beta, d)
+            else:
+                prob.descent_direction(c, p, beta, d, control_time=control_time)
+            ctx.axpby(tl, -1.0, d, 0.0, None, gr)
+
+        def search(dirv, J_k, svals, margins):
+            ctx.source_trials(c, dirv, s0, K, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
+            prob.state(srcB, uB, batch=K)
+            J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs)
+            for k in range(K):
+                ckB.copy_from(c, tl, dst_off=k * tl)
+            dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=K)
+            t, looked = _first_accepted(J, dist, J_k, svals, gam, margins)
+            return t, (None if t is None else float(J[t])), (None if t is None else float(dist[t])), looked
+
+        def take(t):
+            c.copy_from(cB, tl, src_off=t * tl)
+            u.copy_from(uB, tl, src_off=t * tl)
+
+        def stop_test(J, Jt, dist):
+            nc = float(ctx.l2_norm_sq_Q(qn_bufs[1], None, Nt, dt)[0])      # (c_old: the control the step started from)
+            crit["stop_crit"].append(dist / nc if nc > 0 else np.inf)
+            crit["stop_crit2"].append(abs(J - Jt) / abs(J))
+            return not (crit["stop_crit2"][-1] >= tol or (stop == "both" and crit["stop_crit"][-1] >= tol))
+
+        hist = _lbfgs_iterate(ctx, lm, tl, c, gr, qn_bufs, J0, gradient, search, take, c_lower, c_upper, int(max_iters),
+                              gam, s0, K, stop_test)
+        hist.update(crit)
+        return u.download(), p.download(), c.download(), hist
+    finally:
+        lm.close()
+        for a in bufs:
+            a.free()

@@ -363,6 +363,30 @@ int femfct_time_restrict(femfct_ctx* ctx, const double* x_traj, const int32_t* s
 int femfct_time_prolong(femfct_ctx* ctx, const double* y_dev, const int32_t* starts_host, int32_t K, int32_t num_steps,
                         int32_t batch, double* out_traj);
 
+/* Primitives of the limited-memory quasi-Newton loops (solvers.LimitedMemory; an extension, no reference call): a
+ * direction of any memory is one call of each, and the two-loop recursion runs on the host on coefficient vectors. */
+/* The free set of a box-constrained control c with gradient g, one byte per value: mask[k] = 0 (bound) iff
+ * (c[k] <= c_lower && g[k] > 0) || (c[k] >= c_upper && g[k] < 0), else 1 (free).  One launch, does not synchronise. */
+int femfct_free_set(femfct_ctx* ctx, const double* c_dev, const double* g_dev, double c_lower, double c_upper, int64_t count,
+                    uint8_t* mask_dev);
+/* The L2(Q) Gram matrix of J trajectories ((num_steps+1)*n doubles each; fields_host: J device pointers, read before the
+ * call returns; the same pointer may appear twice), 1 <= J <= FEMFCT_MAX_GRAM_FIELDS:
+ *   G_host[i*J + j] = dt * sum_l w_l (chi.f_i)_l^T M (chi.f_j)_l
+ * with the registered mass matrix, the trapezoid weights w_l of femfct_l2_norm_sq_Q and chi = mask_dev (one byte per
+ * value as femfct_free_set writes it; NULL: all free).  Entries i <= j are formed as f_i . (M f_j) and mirrored: G is
+ * exactly symmetric.  The sums run in the fixed tree of femfct_l2_norm_sq_Q (no atomics): two calls return the same
+ * bits, and without a mask G[i][i] = femfct_l2_norm_sq_Q(f_i) bit for bit.  Synchronises. */
+#define FEMFCT_MAX_GRAM_FIELDS 17
+int femfct_q_gram(femfct_ctx* ctx, const double* const* fields_host, int32_t J, const uint8_t* mask_dev, int32_t num_steps,
+                  double dt, double* G_host);
+/* out[k] = ((coef_0*f_0[k] + coef_1*f_1[k]) + ...) + coef_{J-1}*f_{J-1}[k] where mask[k] != 0 (the sum in index order, no
+ * contraction: bitwise the NumPy expression) and fallback_scale*fallback[k] elsewhere.  mask_dev NULL: all free, and only
+ * then may fallback_dev be NULL.  fields_host and coef_host (J values each) are read before the call returns.  out must
+ * not alias an input.  One launch, does not synchronise. */
+int femfct_q_combine(femfct_ctx* ctx, const double* const* fields_host, const double* coef_host, int32_t J,
+                     const uint8_t* mask_dev, const double* fallback_dev, double fallback_scale, int64_t count,
+                     double* out_dev);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
