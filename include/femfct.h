@@ -169,7 +169,11 @@ const double* femfct_lumped_mass(const femfct_ctx* ctx);
 /* FCT_alg_ref(A, rhs, u_n, dt, nodes, M, M_lumped, dof_neighbors, non_flux_mat)
  * helpers.py:1715-1872.  All pointers are device pointers; N_ell and rhs may be
  * NULL (= zero).  batch >= 1 independent systems (see layout above); N_shared != 0
- * means one N_ell is shared by the whole batch.  Asynchronous on the ctx stream. */
+ * means one N_ell is shared by the whole batch.  Asynchronous on the ctx stream.
+ * The low-order solve runs a budget of sweeps that the context adapts from femfct_last_step_info to what the previous
+ * steps needed (it starts anew with every registered pattern).  A member that the budget did not suffice for carries
+ * FEMFCT_FLAG_SOLVER_BUDGET there; femfct_last_step_info then raises the budget, and the step is to be repeated (as
+ * femfct_fct_step_host does by itself) until the flag is gone or the budget has reached femfct_set_solver's max_iters. */
 int femfct_fct_step(femfct_ctx* ctx, const double* A_ell, const double* N_ell, int32_t N_shared,
                     const double* rhs, const double* u_n, double dt, double* u_out, int32_t batch);
 /* diagnostics of the most recent femfct_fct_step (synchronises) */

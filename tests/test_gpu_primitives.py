@@ -24,6 +24,7 @@ import pytest
 from scipy.sparse import csr_matrix
 from scipy.sparse.linalg import spsolve
 
+import generic_patterns as gp
 import primitives_reference as pr
 from regime_helpers import REGIME_KNOBS, nine_point_problem, regime_knobs_default
 
@@ -124,7 +125,8 @@ _CTX = {}
 
 
 def _context(hp, monkeypatch, kind, N, order=None, env=None, fusion=None):
-    """The module's one live context: mesh (set_mesh_square on the unit square) or the width-9 generic pattern."""
+    """The module's one live context: mesh (set_mesh_square on the unit square), the width-9 generic pattern, or one of
+    tests/generic_patterns.py with N its name."""
     env = dict(env or {})
     key = (kind, N, order, tuple(sorted(env.items())), fusion, tuple(os.environ.get(k) for k in REGIME_KNOBS))
     if key not in _CTX:
@@ -137,7 +139,7 @@ def _context(hp, monkeypatch, kind, N, order=None, env=None, fusion=None):
         if kind == "mesh":
             ctx.set_mesh_square(0.0, 1.0, N - 1, order)
         else:
-            M, _ = nine_point_problem(N, np.random.default_rng(N))
+            M, _ = nine_point_problem(N, np.random.default_rng(N)) if kind == "nine" else gp.matrices(N)
             M.sort_indices()
             ctx.set_pattern_csr(M.indptr, M.indices)
             ctx.set_mass(M.data, np.asarray(M.sum(axis=1)).ravel())
@@ -297,7 +299,13 @@ def test_chebsi_md_row_kernels(hp, monkeypatch, spectrum):
 
 # ------------------------------------------------------------------------------------------------ matrix helpers
 PATTERNS = [pytest.param("mesh", N, o, id=f"{o.lower()}-N{N}") for o in ("VERTEX", "FENICS") for N in (2, 9, 46)] + \
-           [pytest.param("nine", 6, None, id="nine-point-N6")]
+           [pytest.param("nine", 6, None, id="nine-point-N6")] + \
+           [pytest.param("generic", name, None, id=name) for name in gp.NAMES]
+
+
+def _seed(N):
+    """N of a mesh, the number of nodes of a named pattern"""
+    return N if isinstance(N, int) else gp.NODES[N]
 
 
 def _pattern(hp, monkeypatch, kind, N, order):
@@ -317,7 +325,7 @@ def test_csr_ell_round_trip_and_transpose(hp, monkeypatch, kind, N, order):
     is bitwise the scipy transpose on the pattern, applied twice it gives the input back; in == out is refused."""
     P = _pattern(hp, monkeypatch, kind, N, order)
     ctx = P.ctx
-    vals = _mixed(np.random.default_rng(N), 1, P.nnz)[0]
+    vals = _mixed(np.random.default_rng(_seed(N)), 1, P.nnz)[0]
     A = csr_matrix((vals, P.indices, P.indptr), shape=(P.n, P.n))
     At = csr_matrix(A.T)
     At.sort_indices()
@@ -344,7 +352,7 @@ def test_spmv(hp, monkeypatch, kind, N, order, B):
     """y = alpha A x + beta y with a matrix per member; with beta = 0 a NaN-filled y must come out finite (never read)."""
     P = _pattern(hp, monkeypatch, kind, N, order)
     ctx = P.ctx
-    rng = np.random.default_rng(10 * N + B)
+    rng = np.random.default_rng(10 * _seed(N) + B)
     vals, x, y0 = _mixed(rng, B, P.nnz), rng.standard_normal((B, P.n)), rng.standard_normal((B, P.n))
     worst = 0.0
     with Dev(ctx) as dev:
@@ -372,7 +380,7 @@ def test_artificial_diffusion(hp, monkeypatch, kind, N, order, B):
     symmetric, padding slots 0, diagonal -sum_j d_ij to (W - 1) u sum |d_ij|."""
     P = _pattern(hp, monkeypatch, kind, N, order)
     ctx = P.ctx
-    k = _mixed(np.random.default_rng(20 * N + B), B, P.nnz)
+    k = _mixed(np.random.default_rng(20 * _seed(N) + B), B, P.nnz)
     wn = P.W * P.n
     worst = 0.0
     with Dev(ctx) as dev:
@@ -615,9 +623,15 @@ def test_bicgstab_batched(hp):
     u = 1 + 0.2 * rng.random(n)
     mats = [M + 1e-3 * (8.6676 * Ad - 0.6 * A + 230.82 * asm.weighted_mass(lambda at: at(u) ** 2)),   # helpers.py:595
             M + 1e-3 * (0.05 * Ad + 100 * M)]                                                            # helpers.py:1308
+    _bicgstab_batched(hp, M, mats, "N=41", rng)
+
+
+def _bicgstab_batched(hp, M, mats, label, rng, B=3):
+    """the body of test_bicgstab_batched for a mass matrix (pattern) M and matrices `mats` on its pattern"""
+    n = M.shape[0]
     ctx = hp.Context(0)
     try:
-        Mc = M.copy()
+        Mc = csr_matrix(M).copy()
         Mc.sort_indices()
         ctx.set_pattern_csr(Mc.indptr, Mc.indices)
         ctx.set_mass(Mc.data, np.asarray(M.sum(axis=1)).ravel())
@@ -640,7 +654,23 @@ def test_bicgstab_batched(hp):
                     worst = max(worst, rel(got[m], xs))
                     assert rel(got[m], xs) < 1e-10, (k, shared, m, info)
                     assert info[m]["solver_resid"] <= 1e-13, (k, shared, m, info)
-                _report("bicgstab", f"N=41 matrix={k} B={B} mat_shared={shared}", worst_vs_spsolve=worst, bar=1e-10,
+                _report("bicgstab", f"{label} matrix={k} B={B} mat_shared={shared}", worst_vs_spsolve=worst, bar=1e-10,
                         worst_resid=max(i["solver_resid"] for i in info), bar_resid=1e-13)
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("name", gp.NAMES)
+def test_bicgstab_batched_generic_patterns(hp, name):
+    """The same on the patterns of tests/generic_patterns.py, with the two non-symmetric matrices a step on them meets:
+    M + dt A and the low-order operator M_L + dt (A - D + 0.05 M).  Same bars."""
+    P = gp.problem(name, 1)
+    indptr, indices = P.M.indptr, P.M.indices
+    a, m = P.A[0].data, P.M.data
+    diag = pr.rows_of(indptr) == indices
+    d = pr.artificial_diffusion_offdiag(indptr, indices, -a)
+    d[diag] = -np.add.reduceat(d, indptr[:-1])
+    low = P.dt * (a - d + 0.05 * m)
+    low[diag] += P.ml
+    mats = [csr_matrix((v, indices, indptr), shape=P.M.shape) for v in (m + P.dt * a, low)]    # stored zeros stay stored
+    _bicgstab_batched(hp, P.M, mats, name, np.random.default_rng(gp.NODES[name]))
