@@ -140,6 +140,7 @@ struct femfct_ctx {
     bool deep_halo = true;      // Jacobi halos 11..13 while every tile gets its own CU (fewer launches)
     bool fuse_flux = true;      // last Chebyshev iterations + flux + limiter in one tile launch (small grids)
     bool fuse_dudt = true;      // du/dt rhs + first Chebyshev iterations in one tile launch (small grids)
+    int tile_lean = 1;          // 32-patch sweep loops: own value in a register, static LDS buffers, live nodes only (FEMFCT_TILE_LEAN)
     bool exact_iters = false;   // last fused launch logs per-sweep residuals (exact sweep count; measured 10 % slower)
     int32_t bandwidth = 0;      // max |col - row| of the pattern
     int32_t strip_k = 0;        // 0: automatic

@@ -65,9 +65,92 @@ __device__ __forceinline__ TileGeom tile_geom(int N) {
     return g;
 }
 
+// ---- lean sweep loops (LEAN = 1, FEMFCT_TILE_LEAN) ----------------------------------------------------
+// The same sweeps with three pieces of work taken out of the loop: the node's own value stays in a register (the
+// thread computed it one sweep earlier), the two LDS buffers are addressed statically (the loop is unrolled by two:
+// neighbour addresses are loop-invariant registers, the buffer is an immediate offset), and a node sweeps only while
+// the owned tile can still see the result: a node at max-norm distance d from the tile influences it through sweep
+// K - 1 - d at the latest.  A node live in sweep k has neighbours that were live in sweep k - 1 (their kvalid and
+// their K - d are lower by one at most), so every value it reads was written into the buffer it reads from; nodes
+// that never update (outside the mesh) are read from both buffers, which therefore both start with the input.
+// Operands and their order are those of the LEAN = 0 loops: the owned values are the same bits.
+template <int H>
+__device__ __forceinline__ int tile_dist(const TileGeom& g) {
+    constexpr int T = TILE_L - 2 * H;
+    const int ddx = max(max(H - g.lx, g.lx - (H + T - 1)), 0), ddy = max(max(H - g.ly, g.ly - (H + T - 1)), 0);
+    return max(ddx, ddy);
+}
+
+struct LeanAddr {
+    const double* n0[6];   // the six neighbours in buffer 0; buffer 1 lies TILE_L * TILE_LD doubles further
+    double* me0;           // the node itself in buffer 0
+};
+
+__device__ __forceinline__ LeanAddr lean_addr(double (*bufs)[TILE_L * TILE_LD], const TileGeom& g) {
+    LeanAddr a;
+    a.me0 = &bufs[0][g.self];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) a.n0[s] = &bufs[0][g.nb[s]];
+    return a;
+}
+
+// K Jacobi sweeps on two initialised buffers (xs[0] = xs[1] = input, barrier passed); returns the node's last iterate.
+// BUF (0 / 1): the buffer a sweep reads; it writes the other one.  LAST: sweep K - 1, whose input's residual is taken
+// (the last sweep is peeled off the loop, so the others carry no residual arithmetic).
+template <int BUF, int LAST>
+__device__ __forceinline__ void lean_jacobi_sweep(const LeanAddr& a, bool live, bool owned, const double* lv, double dg,
+                                                  double rdg, double bv, double& xo, double& rmax) {
+    constexpr int RD = BUF * TILE_L * TILE_LD, WR = (1 - BUF) * TILE_L * TILE_LD;
+    if (live) {
+        double acc = bv;
+#pragma unroll
+        for (int s = 0; s < 6; ++s) acc = fma(-lv[s], a.n0[s][RD], acc);
+        if (LAST && owned) rmax = nan_max(rmax, fabs(acc - dg * xo));
+        xo = acc * rdg;
+        a.me0[WR] = xo;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double lean_jacobi(const LeanAddr& a, int klive, int K, bool owned, const double* lv, double dg,
+                                              double rdg, double bv, double xi, double& rmax) {
+    double xo = xi;
+    int k = 0;
+    for (; k + 2 < K; k += 2) {
+        lean_jacobi_sweep<0, 0>(a, k < klive, owned, lv, dg, rdg, bv, xo, rmax);
+        lean_jacobi_sweep<1, 0>(a, k + 1 < klive, owned, lv, dg, rdg, bv, xo, rmax);
+    }
+    if (k + 1 < K) {
+        lean_jacobi_sweep<0, 0>(a, k < klive, owned, lv, dg, rdg, bv, xo, rmax);
+        lean_jacobi_sweep<1, 1>(a, k + 1 < klive, owned, lv, dg, rdg, bv, xo, rmax);
+    } else if (k < K) {
+        lean_jacobi_sweep<0, 1>(a, k < klive, owned, lv, dg, rdg, bv, xo, rmax);
+    }
+    return xo;
+}
+
+// One Chebyshev iteration of the three-term recurrence on two buffers of y_mid (ym, yo: the node's own y_mid and
+// y_old, rotated in registers).
+template <int BUF>
+__device__ __forceinline__ void lean_cheb_iter(const LeanAddr& a, bool live, const double* mv, double md, double rmd, double bv,
+                                               double wk, double& ym, double& yo) {
+    constexpr int RD = BUF * TILE_L * TILE_LD, WR = (1 - BUF) * TILE_L * TILE_LD;
+    if (live) {
+        double acc = md * ym;
+#pragma unroll
+        for (int s = 0; s < 6; ++s) acc = fma(mv[s], a.n0[s][RD], acc);
+        const double z = (bv - acc) * rmd;
+        const double yn = wk * (z + ym - yo) + yo;
+        yo = ym;
+        ym = yn;
+        a.me0[WR] = yn;
+    }
+    __syncthreads();
+}
+
 // BIG = 1: grids with more workgroups than in-kernel partials (bandwidth regime); the residual maxima
 // go through k_reduce_resid.  A template parameter so that profiles list the two regimes separately.
-template <int H, int EXACT, int BIG>
+template <int H, int EXACT, int BIG, int LEAN>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restrict__ b_, double* __restrict__ xa_,
               double* __restrict__ xb_, double* __restrict__ part, StepCtl* __restrict__ ctl_, int launch, int K,
@@ -145,10 +228,16 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
         xi = xin[g.i];
     }
     xs[0][g.self] = xi;
+    if (LEAN) xs[1][g.self] = xi;          // nodes that never update are read from both buffers
     __syncthreads();
     double rmax = 0.0;
     int cur = 0;
+    [[maybe_unused]] double xo = xi;                             // LEAN: own iterate, a register, never re-read
+    [[maybe_unused]] const int klive = min(g.kvalid, K - tile_dist<H>(g));   // LEAN: sweeps whose result the owned tile can still see
+    [[maybe_unused]] const LeanAddr a = lean_addr(xs, g);
     if (!EXACT) {
+        if constexpr (LEAN) xo = lean_jacobi(a, klive, K, g.owned, lv, dg, rdg, bv, xi, rmax);
+        else
         for (int k = 0; k < K; ++k) {
             const double* c = xs[cur];
             double xn = c[g.self];
@@ -171,6 +260,20 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
         for (int k = 0; k < H; ++k) {
             rk[k] = 0.0;
             if (k < K) {
+                if constexpr (LEAN) {
+                    const int rd = (k & 1) * TILE_L * TILE_LD, wr = ((k + 1) & 1) * TILE_L * TILE_LD;
+                    if (k < klive) {
+                        double acc = bv;
+#pragma unroll
+                        for (int s = 0; s < W - 1; ++s) acc = fma(-lv[s], a.n0[s][rd], acc);
+                        if (g.owned) rk[k] = fabs(acc - dg * xo);
+                        if (k == K - 1) rmax = nan_max(rmax, rk[k]);
+                        xo = acc * rdg;
+                        a.me0[wr] = xo;
+                    }
+                    __syncthreads();
+                    continue;
+                }
                 const double* c = xs[cur];
                 double xn = c[g.self];
                 if (k < g.kvalid) {
@@ -200,7 +303,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
             partk[((int64_t)bz * 16 + threadIdx.x) * FEMFCT_MAX_PARTIALS + wg] = v;
         }
     }
-    if (g.owned) xout[g.i] = xs[cur][g.self];
+    if (g.owned) xout[g.i] = LEAN ? xo : xs[cur][g.self];        // LEAN: no LDS read-back
     rmax = block_reduce(rmax, OpMax(), 0.0, smem);
     if (threadIdx.x == 0) {
         if (BIG) bigpart[(int64_t)bz * nwg + wg] = rmax;
@@ -216,7 +319,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
 // limiter, then K Jacobi sweeps run as in k_tile_jacobi.  Saves one dependent launch per time step.
 // PRE = 1: the operator was built before the sweep (k_low_seq): A_ref is the L_k sequence, read instead of built (no
 // a_ji exchange, no D store: the limiter reads D_k from the sequence); the owned rows of L still go to L_ for launch 1.
-template <int H, int PRE>
+template <int H, int PRE, int LEAN>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, int nshared,
                     VecRef rhs_ref, int64_t rhs_bstride, VecRef u_ref, int64_t u_bstride,
@@ -330,9 +433,13 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
         rsmin = rs;
     }
     xs[0][g.self] = xi;
+    if (LEAN) xs[1][g.self] = xi;          // nodes that never update are read from both buffers
     __syncthreads();
     double rmax = 0.0;
     int cur = 0;
+    [[maybe_unused]] double xo = xi;
+    if constexpr (LEAN) xo = lean_jacobi(lean_addr(xs, g), min(g.kvalid, K - tile_dist<H>(g)), K, g.owned, lv, dg, rdg, bv, xi, rmax);
+    else
     for (int k = 0; k < K; ++k) {
         const double* c = xs[cur];
         double xn = c[g.self];
@@ -347,7 +454,7 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
         __syncthreads();
         cur ^= 1;
     }
-    if (g.owned) xb_[voff + g.i] = xs[cur][g.self];
+    if (g.owned) xb_[voff + g.i] = LEAN ? xo : xs[cur][g.self];
     block_reduce_max_max_min(rmax, bmax, rsmin, smem);
     if (threadIdx.x == 0) {
         p[wg] = rmax;
@@ -409,13 +516,13 @@ k_reduce_resid(const double* __restrict__ bigpart, int64_t count, StepCtl* __res
     if (threadIdx.x == 0) ctl_[bz].rs[launch & 1] = v;
 }
 
-template <int H>
+template <int H, int LEAN>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_cheb(int n, int N, const double* __restrict__ M, const double* __restrict__ b_, const double* __restrict__ ymid_,
             const double* __restrict__ yold_, double* __restrict__ omid_, double* __restrict__ oold_, int K,
             CheOmegas om, double md_scale, ChebIO cio) {
     constexpr int W = 7;
-    __shared__ double ys[3][TILE_L * TILE_LD];
+    __shared__ double ys[LEAN ? 2 : 3][TILE_L * TILE_LD];
     const int64_t voff = (int64_t)blockIdx.z * n;
     if (cio.mat) M = cio.mat + (int64_t)blockIdx.z * cio.mat_bs;
     if (cio.scale_dev) md_scale = cio.scale_dev[blockIdx.z];
@@ -434,6 +541,25 @@ k_tile_cheb(int n, int N, const double* __restrict__ M, const double* __restrict
         bv = b_[voff + g.i];
         if (ymid_) ym = ymid_[voff + g.i];
         if (yold_) yo = yold_[voff + g.i];
+    }
+    if constexpr (LEAN) {
+        // both buffers hold y_mid; y_mid and y_old of the node itself stay in ym, yo
+        ys[0][g.self] = ym;
+        ys[1][g.self] = ym;
+        __syncthreads();
+        const int klive = min(g.kvalid, K - tile_dist<H>(g));
+        const LeanAddr a = lean_addr(ys, g);
+        int k = 0;
+        for (; k + 1 < K; k += 2) {
+            lean_cheb_iter<0>(a, k < klive, mv, md, rmd, bv, omd ? omd[k] : om.w[k], ym, yo);
+            lean_cheb_iter<1>(a, k + 1 < klive, mv, md, rmd, bv, omd ? omd[k + 1] : om.w[k + 1], ym, yo);
+        }
+        if (k < K) lean_cheb_iter<0>(a, k < klive, mv, md, rmd, bv, omd ? omd[k] : om.w[k], ym, yo);
+        if (g.owned) {
+            omid_[voff + g.i] = ym;
+            if (oold_) oold_[voff + g.i] = yo;
+        }
+        return;
     }
     ys[0][g.self] = yo;
     ys[1][g.self] = ym;
@@ -568,14 +694,15 @@ k_tile_flux_limit(int n, int N, double h, const double* __restrict__ M, const do
 // (helpers.py:1818-1870) in one launch: 8 x 8 tile + halo 12 (ten rings for the iterations, two for
 // the limiter: R+- of the ring-1 neighbours).  du never goes to memory.  Same expressions in the same
 // order as k_tile_cheb + k_tile_flux_limit => bitwise the same step.  Latency regime only.
-template <int GEOM>
-__global__ void __launch_bounds__(STRIP_T)
+// (LEAN = 1 compiles to 72 VGPRs when left alone; the waves-per-SIMD bound 8 holds it at the 64 of LEAN = 0, without scratch)
+template <int GEOM, int LEAN>
+__global__ void __launch_bounds__(STRIP_T, LEAN ? 8 : 1)
 k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, const double* __restrict__ b_,
                        const double* __restrict__ ymid_, const double* __restrict__ yold_, int K, CheOmegas om,
                        double md_scale, MatRef D_ref, const double* __restrict__ ulow_,
                        const double* __restrict__ ml, double dt, VecRef out_ref, int64_t out_bstride, EndArgs e) {
     constexpr int W = 7, HH = 12;
-    __shared__ double ys[3][TILE_L * TILE_LD];
+    __shared__ double ys[LEAN ? 2 : 3][TILE_L * TILE_LD];
     __shared__ double su[TILE_L * TILE_LD], srp[TILE_L * TILE_LD], srm[TILE_L * TILE_LD];
     const int bz = blockIdx.z;
     const int64_t voff = (int64_t)bz * n;
@@ -602,7 +729,7 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         ui = ulow_[voff + g.i];
         mli = ml[g.i];
     }
-    ys[0][g.self] = yo;
+    ys[0][g.self] = LEAN ? ym : yo;        // LEAN: both buffers hold y_mid, the node's own y_mid / y_old stay in ym, yo
     ys[1][g.self] = ym;
     su[g.self] = ui;
     srp[g.self] = 1.0;
@@ -616,6 +743,22 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         for (int s = 1; s < W; ++s) dv[s - 1] = D_[(int64_t)s * n + g.i];
     }
     int io = 0, im = 1, in_ = 2;
+    // fluxes where all six neighbours carry the final du (one ring inside the iterations' validity).  LEAN: only where
+    // the owned tile reads R+- (its first ring); there the node and its six neighbours iterated to the end (their
+    // kvalid is at least K), so the last buffer holds their final du.
+    const bool have = g.inside && g.kvalid >= K + 1 && (!LEAN || tile_dist<HH>(g) <= 1);
+    if constexpr (LEAN) {
+        // the fluxes of the tile's first ring need du two rings out: a node stops iterating d - 2 iterations early
+        const int klive = min(g.kvalid, K - max(tile_dist<HH>(g) - 2, 0));
+        const LeanAddr a = lean_addr(ys, g);
+        int k = 0;
+        for (; k + 1 < K; k += 2) {
+            lean_cheb_iter<0>(a, k < klive, mv, md, rmd, bv, om.w[k], ym, yo);
+            lean_cheb_iter<1>(a, k + 1 < klive, mv, md, rmd, bv, om.w[k + 1], ym, yo);
+        }
+        if (k < K) lean_cheb_iter<0>(a, k < klive, mv, md, rmd, bv, om.w[k], ym, yo);
+        im = K & 1;                         // the buffer iteration K - 1 wrote (K = 0: either)
+    } else
     for (int k = 0; k < K; ++k) {
         const double* ymd = ys[im];
         const double ymv = ymd[g.self];
@@ -633,10 +776,8 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         int t = io; io = im; im = in_; in_ = t;
     }
     const double* sd = ys[im];
-    const double dui = sd[g.self];
+    const double dui = LEAN ? ym : sd[g.self];
     double f[W - 1];
-    // fluxes where all six neighbours carry the final du (one ring inside the iterations' validity)
-    const bool have = g.inside && g.kvalid >= K + 1;
     if (have) {
         double pp = 0.0, pm = 0.0, umax = ui, umin = ui;
 #pragma unroll
@@ -675,6 +816,7 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
 //   r = rhs - A u_L (helpers.py:1814), y_1 = w_1 r / Md, then iterations 2..K+1 (helpers.py:175-184).
 // 12 x 12 tile + halo 10: one ring is spent on A u_L, nine on Chebyshev iterations 2..10.
 // Also finalises the low-order solve's bookkeeping (what k_dudt_rhs does in the unfused sequence).
+template <int LEAN>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride,
                  const double* __restrict__ M, const double* __restrict__ xa_, const double* __restrict__ xb_,
@@ -683,7 +825,7 @@ k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride
                  int part_count, int iters_per_unit, double rel_tol, const double* __restrict__ partk, int exact_k,
                  int K, CheOmegas om, double md_scale, double omega1) {
     constexpr int W = 7, H = 10;
-    __shared__ double ys[3][TILE_L * TILE_LD];
+    __shared__ double ys[LEAN ? 2 : 3][TILE_L * TILE_LD];
     __shared__ double smem[64];
     const int bz = blockIdx.z;
     StepCtl* ctl = ctl_ + bz;
@@ -725,16 +867,41 @@ k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride
         ui = x[g.i];
         ri = rhs ? rhs[g.i] : 0.0;
     }
-    ys[2][g.self] = ui;
+    constexpr int UB = LEAN ? 0 : 2;        // the buffer u_L is staged in
+    ys[UB][g.self] = ui;
     __syncthreads();
     // r = rhs - A u_L on every node whose neighbours are in the patch
     double r = 0.0, y1 = 0.0;
     if (g.kvalid >= 1) {
         double acc = av[0] * ui;
 #pragma unroll
-        for (int s = 1; s < W; ++s) acc = fma(av[s], ys[2][g.nb[s - 1]], acc);
+        for (int s = 1; s < W; ++s) acc = fma(av[s], ys[UB][g.nb[s - 1]], acc);
         r = -acc + ri;
         y1 = omega1 * (r / (md_scale * md));
+    }
+    if constexpr (LEAN) {
+        // both buffers hold y_mid = y_1 (buffer 1 first: buffer 0 is still being read as u_L); y_mid and y_old of the
+        // node itself stay in registers.  Iteration 0 reads buffer 1.
+        ys[1][g.self] = y1;
+        __syncthreads();
+        ys[0][g.self] = y1;                 // (own slot only, rewritten by this thread alone before anyone reads it)
+        double ym = y1, yo = 0.0;
+        const int dist = tile_dist<H>(g);
+        const LeanAddr a = lean_addr(ys, g);
+        auto live = [&](int k) { return k + 1 < g.kvalid && k < K - dist; };   // one ring already spent on A u_L
+        int k = 0;
+        for (; k + 1 < K; k += 2) {
+            lean_cheb_iter<1>(a, live(k), mv, md, rmd, r, om.w[k], ym, yo);
+            lean_cheb_iter<0>(a, live(k + 1), mv, md, rmd, r, om.w[k + 1], ym, yo);
+        }
+        if (k < K) lean_cheb_iter<1>(a, live(k), mv, md, rmd, r, om.w[k], ym, yo);
+        if (g.owned) {
+            ulow_[voff + g.i] = ui;
+            rdu_[voff + g.i] = r;
+            omid_[voff + g.i] = ym;
+            if (oold_) oold_[voff + g.i] = yo;
+        }
+        return;
     }
     __syncthreads();
     ys[0][g.self] = 0.0;
@@ -784,7 +951,10 @@ int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, MatRef
     };
     with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
         constexpr int H = decltype(h)::value;
-        if (pre) go(k_tile_build_jacobi<H, 1>); else go(k_tile_build_jacobi<H, 0>);
+        with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+            constexpr int LEAN = decltype(l)::value;
+            if (pre) go(k_tile_build_jacobi<H, 1, LEAN>); else go(k_tile_build_jacobi<H, 0, LEAN>);
+        });
     });
     femfct_prof_end(ctx);
     return FEMFCT_OK;
@@ -812,15 +982,18 @@ int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double
         hipLaunchKernelGGL(kernel, grid, dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, L, b, xa, xb, ctx->d_part, ctx->d_ctl,
                            launch, pl.K, g_build, ctx->rel_tol, bigp, pk, bn_launch, defer_arg);
     };
-    if (big) {
-        go(k_tile_jacobi<8, 0, 1>, 0);
-        femfct_launch_reduce_resid(ctx, (int64_t)pl.tiles * pl.tiles, launch, batch);
-    } else {
-        with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
-            constexpr int H = decltype(h)::value;
-            if (pk && !defer) go(k_tile_jacobi<H, 1, 0>, 0); else go(k_tile_jacobi<H, 0, 0>, defer);
-        });
-    }
+    with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+        constexpr int LEAN = decltype(l)::value;
+        if (big) {
+            go(k_tile_jacobi<8, 0, 1, LEAN>, 0);
+            femfct_launch_reduce_resid(ctx, (int64_t)pl.tiles * pl.tiles, launch, batch);
+        } else {
+            with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
+                constexpr int H = decltype(h)::value;
+                if (pk && !defer) go(k_tile_jacobi<H, 1, 0, LEAN>, 0); else go(k_tile_jacobi<H, 0, 0, LEAN>, defer);
+            });
+        }
+    });
     femfct_prof_end(ctx);
     return FEMFCT_OK;
 }
@@ -846,10 +1019,12 @@ int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, MatRef A, VecRef rhs, int64_t
     double* omid = last ? ctx->d_du : ctx->d_y0;
     double* oold = last ? nullptr : ctx->d_y2;
     femfct_prof_begin(ctx, KC_DUDT_RHS);
-    hipLaunchKernelGGL(k_tile_dudt_cheb, dim3(t, exact_k < 0 ? t + 1 : t, batch), dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, A, rhs,
-                       rhs_bstride, ctx->d_M, ctx->d_xa, ctx->d_xb, ulow, ctx->d_rdu, omid, oold, ctx->d_part, ctx->d_ctl,
-                       budget_units, part_count, iters_per_unit, ctx->rel_tol, exact_k ? ctx->d_partk : nullptr, exact_k,
-                       K, om, md_scale, omegas[0]);
+    with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+        hipLaunchKernelGGL(k_tile_dudt_cheb<decltype(l)::value>, dim3(t, exact_k < 0 ? t + 1 : t, batch), dim3(STRIP_T), 0,
+                           ctx->stream, ctx->n, ctx->N, A, rhs, rhs_bstride, ctx->d_M, ctx->d_xa, ctx->d_xb, ulow, ctx->d_rdu, omid,
+                           oold, ctx->d_part, ctx->d_ctl, budget_units, part_count, iters_per_unit, ctx->rel_tol,
+                           exact_k ? ctx->d_partk : nullptr, exact_k, K, om, md_scale, omegas[0]);
+    });
     femfct_prof_end(ctx);
     if (tail_first) *tail_first = last ? 0 : K + 2;
     if (last || tail_first) return FEMFCT_OK;
@@ -875,8 +1050,11 @@ int femfct_enqueue_tile_cheb(femfct_ctx* ctx, const TilePlan& pl, const double* 
         if (io_in && k0 == k_first) { io.mid_ref = io_in->mid_ref; io.mid_bs = io_in->mid_bs; }
         if (io_in && k1 == k_last + 1) { io.out_ref = io_in->out_ref; io.out_bs = io_in->out_bs; }
         with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
-            hipLaunchKernelGGL((k_tile_cheb<decltype(h)::value>), dim3(pl.tiles, pl.tiles, batch), dim3(STRIP_T), 0, ctx->stream,
-                               ctx->n, ctx->N, ctx->d_M, b, mid, old, omid, oold, k1 - k0, om, md_scale, io);
+            with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+                hipLaunchKernelGGL((k_tile_cheb<decltype(h)::value, decltype(l)::value>), dim3(pl.tiles, pl.tiles, batch),
+                                   dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, ctx->d_M, b, mid, old, omid, oold, k1 - k0, om,
+                                   md_scale, io);
+            });
         });
         femfct_prof_end(ctx);
     });
@@ -907,12 +1085,13 @@ int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const 
     for (int k = k_first; k <= k_last; ++k) om.w[k - k_first] = omegas[k - 1];
     const int t = (ctx->N + 7) / 8;
     femfct_prof_begin(ctx, KC_FLUX);
-    if (femfct_geom_mass(ctx))
-        hipLaunchKernelGGL(k_tile_cheb_flux_limit<1>, dim3(t, t, batch), dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, ctx->h,
-                           ctx->d_M, b, in_mid, in_old, K, om, md_scale, D, ulow, ctx->d_ml, dt, out, out_bstride, e);
-    else
-        hipLaunchKernelGGL(k_tile_cheb_flux_limit<0>, dim3(t, t, batch), dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, ctx->h,
-                           ctx->d_M, b, in_mid, in_old, K, om, md_scale, D, ulow, ctx->d_ml, dt, out, out_bstride, e);
+    with_constant<0, 1>(femfct_geom_mass(ctx), [&](auto gm) {
+        with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+            hipLaunchKernelGGL((k_tile_cheb_flux_limit<decltype(gm)::value, decltype(l)::value>), dim3(t, t, batch), dim3(STRIP_T),
+                               0, ctx->stream, ctx->n, ctx->N, ctx->h, ctx->d_M, b, in_mid, in_old, K, om, md_scale, D, ulow,
+                               ctx->d_ml, dt, out, out_bstride, e);
+        });
+    });
     femfct_prof_end(ctx);
     return FEMFCT_OK;
 }
