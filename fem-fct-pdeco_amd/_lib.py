@@ -162,6 +162,9 @@ SIGNATURES = {
     "femfct_free_set": (C.c_int, [_p, _p, _p, _d, _d, C.c_int64, _p]),
     "femfct_q_gram": (C.c_int, [_p, _p, _i, _p, _i, _d, _p]),
     "femfct_q_combine": (C.c_int, [_p, _p, _p, _i, _p, _p, _d, C.c_int64, _p]),
+    "femfct_prox_trials": (C.c_int, [_p, _p, _p, _p, _d, _i, _d, _d, _d, C.c_int64, _p, _p]),
+    "femfct_l1_norm_Q": (C.c_int, [_p, _p, _i, _d, _p, _i]),
+    "femfct_sparse_trial_stats": (C.c_int, [_p, _p, _p, _i, _i, _d, _p, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -270,6 +270,10 @@ FEMFCT_INTERNAL void femfct_forget_bicgstab_handovers(femfct_ctx* ctx);   // fem
 FEMFCT_INTERNAL void femfct_forget_cheb_off(femfct_ctx* ctx);             // femfct_set_species_solver
 // the reductions' scratch (ctx->d_scratch, kernels_pgd.hip) holds at least `doubles` values; growing it discards its contents
 FEMFCT_INTERNAL int femfct_ensure_scratch(femfct_ctx* ctx, size_t doubles);
+// k_reduce_levels (kernels_pgd.hip) behind a launch that left levels * G partials per batch member:
+// out_dev[b] (+)= scale * sum_l w_l sum_blocks partial[(b*levels + l)*G + block], w_l the trapezoid's when trapezoid != 0
+FEMFCT_INTERNAL void femfct_enqueue_reduce_levels(femfct_ctx* ctx, int32_t batch, int levels, int G, const double* partial,
+                                                  int trapezoid, double scale, int accumulate, double* out_dev);
 
 // graph-key helpers
 static inline uint64_t key_bits(const void* p) { return (uint64_t)(uintptr_t)p; }

@@ -330,14 +330,19 @@ int enqueue_norm(femfct_ctx* ctx, const double* a, const double* b, int64_t a_ls
     double* part = ctx->d_scratch + scratch_off;
     hipLaunchKernelGGL(k_quadform, g.grid, g.block, 0, ctx->stream, ctx->n, ctx->W, ctx->d_cols, ctx->d_M, a, b,
                        a_lstride, b_lstride, part);
-    hipLaunchKernelGGL(k_reduce_levels, dim3(batch), dim3(256), 0, ctx->stream, levels, G, part, trapezoid, scale,
-                       accumulate, out_dev);
+    femfct_enqueue_reduce_levels(ctx, batch, levels, G, part, trapezoid, scale, accumulate, out_dev);
     return FEMFCT_OK;
 }
 
 }  // namespace
 
 int femfct_ensure_scratch(femfct_ctx* ctx, size_t doubles) { return ensure_scratch(ctx, doubles); }
+
+void femfct_enqueue_reduce_levels(femfct_ctx* ctx, int32_t batch, int levels, int G, const double* partial, int trapezoid,
+                                  double scale, int accumulate, double* out_dev) {
+    hipLaunchKernelGGL(k_reduce_levels, dim3(batch), dim3(256), 0, ctx->stream, levels, G, partial, trapezoid, scale,
+                       accumulate, out_dev);
+}
 
 extern "C" {
 

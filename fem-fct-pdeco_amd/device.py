@@ -550,6 +550,31 @@ class Context:
         check(self.handle, lib.femfct_q_combine(self.handle, ptrs, _host_ptr(cf), J, dptr(mask), dptr(fallback),
                                                 float(fallback_scale), int(count), dptr(out)))
 
+    # -- L1-sparse controls (solvers.prox_solidbody, solvers.prox_source_control) ------------------
+    def prox_trials(self, c, d, s0, K, alpha, c_lower, c_upper, count, c_out, src_out=None, g=None):
+        """c_out[t] = clip(soft_threshold(c + s_t d, s_t alpha)) with s_t = s0 / 2^t, the exact prox of
+        s_t alpha |.| + the box indicator value by value, and src_out[t] = g + c_out[t] (c_out[t] without g) for t < K,
+        one launch; member t starts at t*count.  alpha = 0 gives ``source_trials``' values."""
+        check(self.handle, lib.femfct_prox_trials(self.handle, dptr(c), dptr(d), dptr(g), float(s0), int(K), float(alpha),
+                                                  float(c_lower), float(c_upper), int(count), dptr(c_out), dptr(src_out)))
+
+    def l1_norm_Q(self, a, num_steps, dt, batch=1) -> np.ndarray:
+        """dt sum_l w_l sum_i ml_i |a_{l,i}| of every batch member: the nodal-quadrature L1(Q) norm (the trapezoid weights
+        of ``l2_norm_sq_Q``, the lumped mass).  The same bits on every call."""
+        out = np.empty(max(int(batch), 1))
+        check(self.handle, lib.femfct_l1_norm_Q(self.handle, dptr(a), int(num_steps), float(dt), _host_ptr(out), int(batch)))
+        return out
+
+    def sparse_trial_stats(self, c_trials, c_ref, K, num_steps, dt):
+        """``(l1, dist, nnz)`` of the K trial controls ``c_trials`` against the one control ``c_ref``, one fused pass:
+        l1[t] = l1_norm_Q(c_t) and dist[t] = l2_norm_sq_Q(c_t - c_ref) bit for bit, nnz[t] = the count of values != 0
+        (int64)."""
+        k = max(int(K), 1)
+        l1, dist, nnz = np.empty(k), np.empty(k), np.empty(k, dtype=np.int64)
+        check(self.handle, lib.femfct_sparse_trial_stats(self.handle, dptr(c_trials), dptr(c_ref), int(K), int(num_steps),
+                                                         float(dt), _host_ptr(l1), _host_ptr(dist), _host_ptr(nnz)))
+        return l1, dist, nnz
+
     # -- non-FCT species / PDE systems ---------------------------------------------------
     def descent_pointwise(self, count, beta, c, x, out, y=None, scale=1.0, divisor=1.0):
         """out = -(beta*c - t), t = x*y/divisor (y given) or scale*x"""

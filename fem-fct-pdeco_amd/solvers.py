@@ -1312,3 +1312,211 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
         lm.close()
         for a in bufs:
             a.free()
+
+
+# ---------------------------------------------------------------------------------------------- L1-sparse controls
+# An extension (no reference call): the cost gains alpha ||c||_{1,h}, the nodal-quadrature L1(Q) norm
+# dt sum_l w_l sum_i ml_i |c_{l,i}| (trapezoid level weights, lumped mass), and the loops above's projected step
+# becomes a proximal one, c_t = clip(soft_threshold(c - s_t g, s_t alpha)): value by value the exact prox of
+# s_t alpha |.| + the box indicator.  It is the nodal discretisation of the continuous proximal-gradient step, the same
+# approximation the loops above make when they clip value by value under the consistent-mass metric.
+def _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha, c_lower, c_upper, max_iters, gam, s0, K,
+                  tol):
+    """The iteration both proximal-gradient loops share.  ``gradient()`` runs the adjoint at the current (c, u) and returns
+    the device direction d = -g; ``trial_costs(d)`` writes the K trial controls into ``cB``, runs their states as one
+    batch and returns the K smooth costs J(S(c_t), c_t); ``take(t)`` makes trial t the iterate."""
+    hist = dict(cost=[], cost_smooth=[], l1=[], nonzero_fraction=[], residual=[], armijo_k=[], step=[], armijo_margin=[],
+                rel_change=[], sweeps=[], wall=[], wall0=time.perf_counter(), stalled=False)
+    svals = [s0 * (1 / 2 ** k) for k in range(K)]
+    F = J0 + alpha * float(ctx.l1_norm_Q(c, Nt, dt)[0])
+    hist["cost0"] = F
+    sweeps = 1
+    for _ in range(max_iters):
+        d = gradient()
+        sweeps += 1
+        ctx.prox_trials(c, d, 1.0, 1, alpha, c_lower, c_upper, tl, cB)       # prox(c - g; tau = alpha), in trial 0's place
+        residual = float(ctx.l2_norm_sq_Q(cB, c, Nt, dt)[0])
+        J = trial_costs(d)
+        l1, dist, nnz = ctx.sparse_trial_stats(cB, c, K, Nt, dt)
+        margins, found = [], None
+        for t, s in enumerate(svals):
+            Ft = float(J[t]) + alpha * float(l1[t])
+            margins.append((Ft - F + gam / s * float(dist[t])) / abs(F))
+            if Ft - F <= -gam / s * float(dist[t]):
+                found = t
+                break
+        sweeps += len(margins)
+        if found is None:
+            hist["stalled"] = True
+            break
+        take(found)
+        for key, v in (("cost", Ft), ("cost_smooth", float(J[found])), ("l1", float(l1[found])),
+                       ("nonzero_fraction", int(nnz[found]) / tl), ("residual", residual), ("armijo_k", found + 1),
+                       ("step", svals[found]), ("armijo_margin", margins), ("rel_change", abs(F - Ft) / abs(F)),
+                       ("sweeps", sweeps), ("wall", time.perf_counter())):
+            hist[key].append(v)
+        F = Ft
+        if tol is not None and hist["rel_change"][-1] < tol:
+            break
+    hist["iterations"] = len(hist["cost"])
+    hist["armijo_margin_min"] = min((abs(m) for ms in hist["armijo_margin"] for m in ms), default=None)
+    return hist
+
+
+def _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time):
+    """the argument validation of the L-BFGS loops, and alpha >= 0; returns (K, u0, uhat, c0) as flat float64 arrays"""
+    snap = _need_obs(optim, obs)
+    alltime = optim == "alltime" or snap
+    n, Nt, tl = prob.n, prob.num_steps, prob.tlen
+    K = int(max_armijo)
+    if not 1 <= K <= _lib.MAX_TRIALS:
+        raise ValueError(f"max_armijo = {K}: must be in 1..{_lib.MAX_TRIALS}")
+    if not alpha >= 0:
+        raise ValueError(f"alpha = {alpha}: must be >= 0")
+    if not c_lower <= c_upper:
+        raise ValueError(f"c_lower = {c_lower} > c_upper = {c_upper}")
+    uhat = np.asarray(uhat, dtype=np.float64).ravel()
+    if uhat.size != (tl if alltime else n):
+        raise ValueError(f"target of {uhat.size} values, expected {tl if alltime else n} for optim='{optim}'")
+    c0 = np.asarray(c0, dtype=np.float64).ravel()
+    if c0.size != tl:
+        raise ValueError(f"c0 of {c0.size} values, expected {tl}")
+    if g is not None and np.asarray(g).size != tl:
+        raise ValueError(f"g of {np.asarray(g).size} values, expected {tl}")
+    u0 = np.asarray(u0, dtype=np.float64).ravel()
+    if u0.size != n:
+        raise ValueError(f"u0 of {u0.size} values, expected {n}")
+    if control_time is not None:
+        control_time.need(c0, n, Nt)
+    return K, u0, uhat, c0
+
+
+def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_upper, iters, gam=1e-4, s0=1.0,
+                   max_armijo=10, tol=None, optim="finaltime", obs=None, control_time=None):
+    """Proximal gradient descent for the drift-control problem with an L1 term: minimises
+    F(c) = J(S(c), c) + alpha ||c||_{1,h} over the box, J the cost of :func:`lbfgs_solidbody` and
+    ||c||_{1,h} = dt sum_l w_l sum_i ml_i |c_{l,i}| (``Context.l1_norm_Q``).  Per iteration, at the control c with
+    u = S(c) and F:
+
+        adjoint(c, u) -> g = -descent_direction (projected with ``control_time``) -> residual
+        ||prox(c - g; alpha) - c||^2_Q -> trials c_t = clip(soft_threshold(c - s_t g, s_t alpha)), s_t = s0/2^t, their
+        ``max_armijo`` states as one batched sweep: accept the first with F(c_t) - F <= -gam/s_t ||c_t - c||^2_Q
+
+    If no trial is accepted the loop stops with ``history["stalled"] = True`` and c unchanged; there is no unconditional
+    first step, so an accepted cost never exceeds the previous one.  ``alpha = 0`` is ``lbfgs_solidbody(memory=0)``.
+    ``tol`` stops on rel_change = |F - F_t| / |F|.  With ``control_time`` c and g are constant on every interval and the
+    prox acts value by value, so the iterates stay piecewise constant bit for bit.  ``optim``, ``obs``: as in
+    pgd_solidbody.
+
+    Returns ``(u, p, c, history)``; history: ``cost`` (F), ``cost_smooth`` (J), ``l1``, ``nonzero_fraction``, ``residual``
+    (at the control the iteration started from), ``armijo_k``, ``step``, ``armijo_margin`` (every trial looked at,
+    (F_t - F + gam/s_t dist_t) / |F|), ``armijo_margin_min``, ``rel_change``, ``sweeps`` (as the L-BFGS loops count
+    them), ``wall``, ``wall0``, ``cost0``, ``stalled``, ``iterations``.  Every list has one entry per accepted step: an
+    iteration that stalls, as in the L-BFGS loops, leaves no entry (its residual and the margins of its ``max_armijo``
+    rejected trials are not kept, so a run that stalls at once has ``armijo_margin_min`` None)."""
+    K, u0, uhat, c0 = _prox_arguments(prob, u0, uhat, c0, None, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time)
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    try:
+        u, p, d, rhs = alloc(tl), alloc(tl), alloc(tl), alloc(tl, False)
+        c = alloc(tl, False).upload(c0)
+        uh = alloc(uhat.size, False).upload(uhat)
+        uhB = alloc(K * uhat.size, False)
+        cB, uB = alloc(K * tl), alloc(K * tl)
+        u0d = alloc(n, False).upload(u0)
+        u.copy_from(u0d, n)
+        for k in range(K):
+            uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
+            uB.copy_from(u0d, n, dst_off=k * tl)          # level 0 of every trial trajectory = the initial condition
+        cost = lambda uu, hh, cc, b: prob.cost(uu, hh, cc, beta, optim, batch=b, obs=obs)
+        prob.forward(c, u, batch=1)
+        J0 = float(cost(u, uh, c, 1)[0])
+
+        def gradient():
+            prob.adjoint(c, u, uh, p, optim, batch=1, obs=obs)
+            if control_time is None:
+                prob.descent_direction(c, u, p, beta, d, scratch=rhs)
+            else:
+                prob.descent_direction(c, u, p, beta, d, scratch=rhs, control_time=control_time)
+            return d
+
+        def trial_costs(dirv):
+            ctx.prox_trials(c, dirv, s0, K, alpha, c_lower, c_upper, tl, cB)
+            prob.forward(cB, uB, batch=K)
+            return cost(uB, uhB, cB, K)
+
+        def take(t):
+            c.copy_from(cB, tl, src_off=t * tl)
+            u.copy_from(uB, tl, src_off=t * tl)
+
+        hist = _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha, c_lower, c_upper, int(iters),
+                             gam, s0, K, tol)
+        return u.download(), p.download(), c.download(), hist
+    finally:
+        for a in bufs:
+            a.free()
+
+
+def prox_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, alpha, c_lower, c_upper, g=None, optim="alltime",
+                        gam=1e-4, s0=1.0, max_armijo=10, tol=None, max_iters=1000, obs=None, control_time=None):
+    """Proximal gradient descent for the linear source-control problem (:class:`LinearSourceControl`,
+    :class:`LinearReactionSourceControl`) with an L1 term: the iteration of :func:`prox_solidbody` with the gradient
+    -descent_direction = beta c - p, the trial controls and sources g + c_t of ``femfct_prox_trials`` in one launch and the
+    ``max_armijo`` trial states as one batched sweep, as :func:`lbfgs_source_control` runs them.  ``alpha = 0`` is
+    ``lbfgs_source_control(memory=0)``'s iteration.  Runs ``max_iters`` iterations, or until rel_change < ``tol``.
+    Arguments as lbfgs_source_control; return value and history as prox_solidbody."""
+    K, u0, uhat, c0 = _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time)
+    snap = _need_obs(optim, obs)
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    try:
+        u, p, d, c = alloc(tl), alloc(tl), alloc(tl), alloc(tl, False).upload(c0)
+        u.upload(np.concatenate([u0, np.zeros(tl - n)]))
+        uh = alloc(uhat.size, False).upload(uhat)
+        gd = None if g is None else alloc(tl, False).upload(g)
+        src = c if gd is None else alloc(tl, False)
+        cB, uB, uhB = alloc(K * tl, False), alloc(K * tl), alloc(K * uhat.size, False)
+        srcB = cB if gd is None else alloc(K * tl, False)
+        for k in range(K):
+            uB.copy_from(u, n, dst_off=k * tl)              # level 0 of every trial state = u0
+            uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
+        if gd is not None:
+            ctx.axpby(tl, 1.0, gd, 1.0, c, src)
+        prob.state(src, u, batch=1)
+        J0 = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs)[0])
+
+        def gradient():
+            prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs) if snap else prob.adjoint_state(u, uh, p, optim, batch=1)
+            if control_time is None:
+                prob.descent_direction(c, p, beta, d)
+            else:
+                prob.descent_direction(c, p, beta, d, control_time=control_time)
+            return d
+
+        def trial_costs(dirv):
+            ctx.prox_trials(c, dirv, s0, K, alpha, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
+            prob.state(srcB, uB, batch=K)
+            return prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs)
+
+        def take(t):
+            c.copy_from(cB, tl, src_off=t * tl)
+            u.copy_from(uB, tl, src_off=t * tl)
+
+        hist = _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha, c_lower, c_upper,
+                             int(max_iters), gam, s0, K, tol)
+        return u.download(), p.download(), c.download(), hist
+    finally:
+        for a in bufs:
+            a.free()

@@ -391,6 +391,27 @@ int femfct_q_combine(femfct_ctx* ctx, const double* const* fields_host, const do
                      const uint8_t* mask_dev, const double* fallback_dev, double fallback_scale, int64_t count,
                      double* out_dev);
 
+/* Primitives of the proximal-gradient loops for L1-sparse controls (solvers.prox_solidbody, solvers.prox_source_control;
+ * an extension, no reference call).  The cost gains alpha * ||c||_{1,h} with the nodal-quadrature norm
+ *   ||c||_{1,h} = dt * sum_l w_l sum_i ml_i |c_{l,i}|
+ * (w_l the trapezoid weights of femfct_l2_norm_sq_Q, ml the registered lumped mass), whose prox is pointwise. */
+/* The K trial controls of a proximal step, t < K, s_t = s0 * (1 / 2^t):
+ *   x = c + s_t*d, tau = s_t*alpha, v = |x| - tau > 0 ? copysign(|x| - tau, x) : 0.0, c_out[t*count + k] = fmin(fmax(v, c_lower), c_upper)
+ * evaluated in this order without contraction (the exact prox of tau|.| + the box indicator, value by value), and
+ * src_out[t*count ..] = g + c_t as femfct_source_trials writes it (g NULL: c_t; src_out may be NULL).  alpha = 0 gives
+ * femfct_source_trials' values.  alpha < 0, K outside 1..FEMFCT_MAX_TRIALS, count <= 0 or c_lower > c_upper is
+ * FEMFCT_ERR_INVALID.  c_out / src_out must not alias an input.  One launch, does not synchronise. */
+int femfct_prox_trials(femfct_ctx* ctx, const double* c_dev, const double* d_dev, const double* g_dev, double s0, int32_t K,
+                       double alpha, double c_lower, double c_upper, int64_t count, double* c_out_dev, double* src_out_dev);
+/* out_host[b] = ||a_b||_{1,h} for the batch trajectories a ((num_steps+1)*n doubles each).  The sums run in the fixed
+ * tree of femfct_l2_norm_sq_Q (no atomics): two calls return the same bits; levels * batch is not limited.  Synchronises. */
+int femfct_l1_norm_Q(femfct_ctx* ctx, const double* a_dev, int32_t num_steps, double dt, double* out_host, int32_t batch);
+/* For the K trial controls c_trials_dev (K trajectories, as femfct_prox_trials writes them) and the one control c_ref_dev
+ * they started from, in one fused pass: l1_host[t] = femfct_l1_norm_Q(c_t) and dist_host[t] = femfct_l2_norm_sq_Q(c_t -
+ * c_ref), both bit for bit, and nnz_host[t] = the number of values of c_t that are != 0.  Synchronises. */
+int femfct_sparse_trial_stats(femfct_ctx* ctx, const double* c_trials_dev, const double* c_ref_dev, int32_t K,
+                              int32_t num_steps, double dt, double* l1_host, double* dist_host, int64_t* nnz_host);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
