@@ -141,6 +141,8 @@ struct femfct_ctx {
     bool fuse_flux = true;      // last Chebyshev iterations + flux + limiter in one tile launch (small grids)
     bool fuse_dudt = true;      // du/dt rhs + first Chebyshev iterations in one tile launch (small grids)
     int tile_lean = 1;          // 32-patch sweep loops: own value in a register, static LDS buffers, live nodes only (FEMFCT_TILE_LEAN)
+    int tile_cone = 0;          // lean loops: liveness and loads by the hexagonal dependency cone of the P1 stencil (FEMFCT_TILE_CONE; needs tile_lean; off: measured no faster)
+    int tile_fit = 1;           // fused du/dt and limiter launches: 6 x 6 tiles on 26 / 30 patches while every workgroup gets a CU (FEMFCT_TILE_FIT; needs tile_lean)
     bool exact_iters = false;   // last fused launch logs per-sweep residuals (exact sweep count; measured 10 % slower)
     int32_t bandwidth = 0;      // max |col - row| of the pattern
     int32_t strip_k = 0;        // 0: automatic
@@ -306,6 +308,10 @@ struct TilePlan { int tiles, K, H; };
 bool femfct_tile_plan(const femfct_ctx* ctx, TilePlan* pl, bool need_partials = true, int budget = 0, int batch = 1);
 bool femfct_tile_big(const femfct_ctx* ctx, const TilePlan& pl);   // more workgroups than in-kernel partials
 bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch);
+bool femfct_tile_fit(const femfct_ctx* ctx, int32_t batch);
+#ifdef FEMFCT_TUNING
+void femfct_tile_phase_dump(const char* path);   // phase stamps of the tile kernels (kernels_tile32.hip), FEMFCT_TILE_TRACE=<file>
+#endif
 bool femfct_geom_mass(const femfct_ctx* ctx);   // M may be derived from the cell geometry instead of loaded
 int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, struct MatRef A, const double* Nm, int32_t nshared,
                                      struct VecRef rhs, int64_t rhs_bstride, struct VecRef u_n, int64_t u_bstride, double dt,

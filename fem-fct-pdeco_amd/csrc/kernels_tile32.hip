@@ -10,7 +10,8 @@
 // node's matrix row in registers, the iterate in LDS -- and runs up to H sweeps per launch (the halo shrinks by one
 // ring per sweep).  H = 8 on large grids (least re-reading), 8..13 in the latency regime (fewest launches: see
 // femfct_tile_plan).  Compared with row strips there is no column table to load and the work spreads over
-// (N / (32 - 2H))^2 workgroups.
+// (N / (32 - 2H))^2 workgroups.  The two fused launches behind the Jacobi solve also run on fitted patches of 26 and 30
+// nodes per side (6 x 6 tiles, FEMFCT_TILE_FIT: femfct_tile_fit) while every workgroup gets a compute unit of its own.
 #include "femfct_internal.h"
 #include "device_utils.h"
 #include "solve_ctl.h"
@@ -28,9 +29,29 @@
 
 namespace {
 
+// Phase stamps of the four launches of a latency-regime step (make tuning; FEMFCT_TILE_TRACE=<file>): thread 0 of a
+// workgroup in the middle of the grid reads the 100 MHz clock at entry, once every load of the load phase is back
+// (behind the barrier that publishes the staged iterate) and at the end, and adds the two differences to sums that
+// femfct_tile_phase_dump writes out.  Read the shares, not the lengths.  The product library carries none of it.
+#ifdef FEMFCT_TUNING
+__device__ unsigned long long g_tile_phase[4][4];        // [kernel][ticks of the load phase, ticks in all, launches, unused]
+#define TILE_STAMP_BEGIN()                                                                                              \
+    unsigned long long ts0_ = 0, ts1_ = 0;                                                                              \
+    const bool ts_on_ = threadIdx.x == 0 && blockIdx.z == 0 && blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.x / 2; \
+    if (ts_on_) ts0_ = __builtin_amdgcn_s_memrealtime()
+#define TILE_STAMP_LOADED() do { if (ts_on_) { __builtin_amdgcn_s_waitcnt(0); ts1_ = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#define TILE_STAMP_END(id) do { if (ts_on_) {                                                                           \
+        const unsigned long long ts2_ = __builtin_amdgcn_s_memrealtime();                                               \
+        g_tile_phase[id][0] += ts1_ - ts0_; g_tile_phase[id][1] += ts2_ - ts0_; g_tile_phase[id][2] += 1; } } while (0)
+#else
+#define TILE_STAMP_BEGIN() do { } while (0)
+#define TILE_STAMP_LOADED() do { } while (0)
+#define TILE_STAMP_END(id) do { } while (0)
+#endif
+
 struct TileGeom {
     int lx, ly, gx, gy, i;
-    bool inside, owned;
+    bool inside, owned;      // (both false for the spare threads of a patch that is no whole number of waves)
     int kvalid;          // the node's value is exact for sweeps k < kvalid
     int nb[6];           // LDS offsets of the six neighbours (clamped into the patch)
     int self;
@@ -62,7 +83,20 @@ __device__ __forceinline__ TileGeom tile_geom(int N) {
         int nx = min(max(g.lx + dx[s], 0), PL - 1), ny = min(max(g.ly + dy[s], 0), PL - 1);
         g.nb[s] = ny * PLD + nx;
     }
+    // a patch of PL^2 nodes that is no whole number of waves: the block is rounded up and the spare threads own no node --
+    // they load nothing, never update, write no LDS slot (tile_spare) and only reach the barriers
+    if (PL * PL % WAVE != 0 && threadIdx.x >= PL * PL) {
+        g.inside = g.owned = false;
+        g.i = 0;
+        g.kvalid = 0;
+        g.self = 0;
+    }
     return g;
+}
+
+template <int PL>
+__device__ __forceinline__ bool tile_spare() {
+    return PL * PL % WAVE != 0 && threadIdx.x >= PL * PL;
 }
 
 // ---- lean sweep loops (LEAN = 1, FEMFCT_TILE_LEAN) ----------------------------------------------------
@@ -74,19 +108,40 @@ __device__ __forceinline__ TileGeom tile_geom(int N) {
 // their K - d are lower by one at most), so every value it reads was written into the buffer it reads from; nodes
 // that never update (outside the mesh) are read from both buffers, which therefore both start with the input.
 // Operands and their order are those of the LEAN = 0 loops: the owned values are the same bits.
-template <int H>
+template <int H, int PL = TILE_L>
 __device__ __forceinline__ int tile_dist(const TileGeom& g) {
-    constexpr int T = TILE_L - 2 * H;
+    constexpr int T = PL - 2 * H;
     const int ddx = max(max(H - g.lx, g.lx - (H + T - 1)), 0), ddy = max(max(H - g.ly, g.ly - (H + T - 1)), 0);
     return max(ddx, ddy);
 }
 
+// CONE (LEAN = 2, FEMFCT_TILE_CONE): the distance of the stencil's own graph instead of the max-norm.  The six
+// neighbours are E, NE, N, W, SW, S, so one step along (1, 1) is one sweep and one step along (1, -1) is two: k sweeps
+// reach a hexagon, and the NW and SE corners of the patch lie outside the owned tile's cone.  With ex, ey the signed
+// excess beyond the tile, d = max(|ex|, |ey|) where they agree in sign and |ex| + |ey| where they do not.  d changes
+// by at most one along each of the six slots, which is all the argument above uses.  Beside the liveness the cone
+// also decides what a thread loads: the matrix row only where the node will ever be live, the iterate only where a
+// live node reads it (d <= K); the others put the zeros of their defaults into LDS.
+template <int H, int PL = TILE_L>
+__device__ __forceinline__ int tile_hexdist(const TileGeom& g) {
+    constexpr int T = PL - 2 * H;
+    const int ex = g.lx - min(max(g.lx, H), H + T - 1), ey = g.ly - min(max(g.ly, H), H + T - 1);
+    return max(max(abs(ex), abs(ey)), abs(ex - ey));      // (|ex - ey| is |ex| + |ey| where the signs differ, and no more than the larger where not)
+}
+
+template <int H, int LEAN, int PL = TILE_L>
+__device__ __forceinline__ int lean_dist(const TileGeom& g) {
+    if constexpr (LEAN == 2) return tile_hexdist<H, PL>(g);
+    else return tile_dist<H, PL>(g);
+}
+
 struct LeanAddr {
-    const double* n0[6];   // the six neighbours in buffer 0; buffer 1 lies TILE_L * TILE_LD doubles further
+    const double* n0[6];   // the six neighbours in buffer 0; buffer 1 lies PL * (PL + 1) doubles further
     double* me0;           // the node itself in buffer 0
 };
 
-__device__ __forceinline__ LeanAddr lean_addr(double (*bufs)[TILE_L * TILE_LD], const TileGeom& g) {
+template <int PL>
+__device__ __forceinline__ LeanAddr lean_addr(double (*bufs)[PL * (PL + 1)], const TileGeom& g) {
     LeanAddr a;
     a.me0 = &bufs[0][g.self];
 #pragma unroll
@@ -131,10 +186,10 @@ __device__ __forceinline__ double lean_jacobi(const LeanAddr& a, int klive, int 
 
 // One Chebyshev iteration of the three-term recurrence on two buffers of y_mid (ym, yo: the node's own y_mid and
 // y_old, rotated in registers).
-template <int BUF>
+template <int BUF, int PL = TILE_L>
 __device__ __forceinline__ void lean_cheb_iter(const LeanAddr& a, bool live, const double* mv, double md, double rmd, double bv,
                                                double wk, double& ym, double& yo) {
-    constexpr int RD = BUF * TILE_L * TILE_LD, WR = (1 - BUF) * TILE_L * TILE_LD;
+    constexpr int RD = BUF * PL * (PL + 1), WR = (1 - BUF) * PL * (PL + 1);
     if (live) {
         double acc = md * ym;
 #pragma unroll
@@ -215,11 +270,24 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
     const double* L = L_ + moff;
     const double* xin = ((launch & 1) ? xb_ : xa_) + voff;
     double* xout = ((launch & 1) ? xa_ : xb_) + voff;
+    TILE_STAMP_BEGIN();
     const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
+    constexpr bool CONE = LEAN == 2;
     double lv[W - 1], dg = 1.0, rdg = 1.0, bv = 0.0, xi = 0.0;
 #pragma unroll
     for (int s = 0; s < W - 1; ++s) lv[s] = 0.0;
-    if (g.inside) {
+    if constexpr (CONE) {
+        // the row only where the node is ever live, the iterate only where a live node reads it
+        const int dist = tile_hexdist<H>(g);
+        if (g.inside && ((dist < K && g.kvalid > 0) || g.owned)) {
+            dg = L[g.i];
+            rdg = 1.0 / dg;
+#pragma unroll
+            for (int s = 1; s < W; ++s) lv[s - 1] = L[(int64_t)s * n + g.i];
+            bv = b_[voff + g.i];
+        }
+        if (g.inside && dist <= K) xi = xin[g.i];
+    } else if (g.inside) {
         dg = L[g.i];
         rdg = 1.0 / dg;
 #pragma unroll
@@ -230,11 +298,12 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
     xs[0][g.self] = xi;
     if (LEAN) xs[1][g.self] = xi;          // nodes that never update are read from both buffers
     __syncthreads();
+    TILE_STAMP_LOADED();
     double rmax = 0.0;
     int cur = 0;
     [[maybe_unused]] double xo = xi;                             // LEAN: own iterate, a register, never re-read
-    [[maybe_unused]] const int klive = min(g.kvalid, K - tile_dist<H>(g));   // LEAN: sweeps whose result the owned tile can still see
-    [[maybe_unused]] const LeanAddr a = lean_addr(xs, g);
+    [[maybe_unused]] const int klive = min(g.kvalid, K - lean_dist<H, LEAN>(g));   // LEAN: sweeps whose result the owned tile can still see
+    [[maybe_unused]] const LeanAddr a = lean_addr<TILE_L>(xs, g);
     if (!EXACT) {
         if constexpr (LEAN) xo = lean_jacobi(a, klive, K, g.owned, lv, dg, rdg, bv, xi, rmax);
         else
@@ -310,6 +379,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
         else if (defer) partk[((int64_t)bz * 16 + launch) * FEMFCT_MAX_PARTIALS + wg] = rmax;   // one slot per launch
         else p[(launch & 1) * FEMFCT_MAX_PARTIALS + wg] = rmax;
     }
+    TILE_STAMP_END(1);
 }
 
 // Launch 0 of the low-order solve with the construction of the low-order operator folded in
@@ -344,6 +414,7 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
     const double* rhs = vec_ptr(rhs_ref);
     if (rhs) rhs += bz * rhs_bstride;
     const double* u = vec_ptr(u_ref) + bz * u_bstride;
+    TILE_STAMP_BEGIN();
     const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
     double lv[W - 1], dv[W - 1], dsum = 0.0, rs = 0.0;
     double dg = 1.0, rdg = 1.0, bv = 0.0, xi = 0.0;
@@ -351,19 +422,39 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
         // the rows k_low_seq built (bitwise those of the branch below); the row sum in the same order
 #pragma unroll
         for (int s = 0; s < W - 1; ++s) lv[s] = 0.0;
-        if (g.inside) {
-            dg = A[g.i];
+        if constexpr (LEAN == 2) {
+            // CONE: the row, M_L and the rhs only where the node is ever live, u^n only where a live node reads it
+            const int dist = tile_hexdist<H>(g);
+            const bool row = g.inside && ((dist < K && g.kvalid > 0) || g.owned);
+            if (row) {
+                dg = A[g.i];
 #pragma unroll
-            for (int s = 1; s < W; ++s) lv[s - 1] = A[(int64_t)s * n + g.i];
-        }
+                for (int s = 1; s < W; ++s) lv[s - 1] = A[(int64_t)s * n + g.i];
+            }
 #pragma unroll
-        for (int s = 0; s < W - 1; ++s) rs += lv[s];
-        if (g.inside) {
-            const double mli = ml[g.i];
-            rs += dg;
-            rdg = 1.0 / dg;
-            xi = u[g.i];
-            bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+            for (int s = 0; s < W - 1; ++s) rs += lv[s];
+            if (g.inside && dist <= K) xi = u[g.i];
+            if (row) {
+                const double mli = ml[g.i];
+                rs += dg;
+                rdg = 1.0 / dg;
+                bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+            }
+        } else {
+            if (g.inside) {
+                dg = A[g.i];
+#pragma unroll
+                for (int s = 1; s < W; ++s) lv[s - 1] = A[(int64_t)s * n + g.i];
+            }
+#pragma unroll
+            for (int s = 0; s < W - 1; ++s) rs += lv[s];
+            if (g.inside) {
+                const double mli = ml[g.i];
+                rs += dg;
+                rdg = 1.0 / dg;
+                xi = u[g.i];
+                bv = mli * xi + (rhs ? dt * rhs[g.i] : 0.0);
+            }
         }
     } else {
         // neighbour s exists in the grid (otherwise the ELL slot is padding: column = row, value 0)
@@ -435,10 +526,11 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
     xs[0][g.self] = xi;
     if (LEAN) xs[1][g.self] = xi;          // nodes that never update are read from both buffers
     __syncthreads();
+    TILE_STAMP_LOADED();
     double rmax = 0.0;
     int cur = 0;
     [[maybe_unused]] double xo = xi;
-    if constexpr (LEAN) xo = lean_jacobi(lean_addr(xs, g), min(g.kvalid, K - tile_dist<H>(g)), K, g.owned, lv, dg, rdg, bv, xi, rmax);
+    if constexpr (LEAN) xo = lean_jacobi(lean_addr<TILE_L>(xs, g), min(g.kvalid, K - lean_dist<H, LEAN>(g)), K, g.owned, lv, dg, rdg, bv, xi, rmax);
     else
     for (int k = 0; k < K; ++k) {
         const double* c = xs[cur];
@@ -461,6 +553,7 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
         p[2 * FEMFCT_MAX_PARTIALS + wg] = bmax;
         p[3 * FEMFCT_MAX_PARTIALS + wg] = rsmin;
     }
+    TILE_STAMP_END(0);
 }
 
 // The low-order operator of every entry of a pre-assembled sequence, once before the sweep (FEMFCT_PREBUILD_LOW):
@@ -530,10 +623,23 @@ k_tile_cheb(int n, int N, const double* __restrict__ M, const double* __restrict
     if (cio.mid_ref.base) ymid_ = vec_ptr(cio.mid_ref) + (int64_t)blockIdx.z * cio.mid_bs - voff;
     if (cio.out_ref.base) omid_ = const_cast<double*>(vec_ptr(cio.out_ref)) + (int64_t)blockIdx.z * cio.out_bs - voff;
     const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
+    constexpr bool CONE = LEAN == 2;
     double mv[W - 1], md = 1.0, rmd = 1.0, bv = 0.0, ym = 0.0, yo = 0.0;
 #pragma unroll
     for (int s = 0; s < W - 1; ++s) mv[s] = 0.0;
-    if (g.inside) {
+    if constexpr (CONE) {
+        // the row and y_old only where the node is ever live, y_mid only where a live node reads it
+        const int dist = tile_hexdist<H>(g);
+        if (g.inside && ((dist < K && g.kvalid > 0) || g.owned)) {
+            md = M[g.i];
+            rmd = 1.0 / (md_scale * md);
+#pragma unroll
+            for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+            bv = b_[voff + g.i];
+            if (yold_) yo = yold_[voff + g.i];
+        }
+        if (g.inside && dist <= K && ymid_) ym = ymid_[voff + g.i];
+    } else if (g.inside) {
         md = M[g.i];
         rmd = 1.0 / (md_scale * md);
 #pragma unroll
@@ -547,8 +653,8 @@ k_tile_cheb(int n, int N, const double* __restrict__ M, const double* __restrict
         ys[0][g.self] = ym;
         ys[1][g.self] = ym;
         __syncthreads();
-        const int klive = min(g.kvalid, K - tile_dist<H>(g));
-        const LeanAddr a = lean_addr(ys, g);
+        const int klive = min(g.kvalid, K - lean_dist<H, LEAN>(g));
+        const LeanAddr a = lean_addr<TILE_L>(ys, g);
         int k = 0;
         for (; k + 1 < K; k += 2) {
             lean_cheb_iter<0>(a, k < klive, mv, md, rmd, bv, omd ? omd[k] : om.w[k], ym, yo);
@@ -695,23 +801,55 @@ k_tile_flux_limit(int n, int N, double h, const double* __restrict__ M, const do
 // the limiter: R+- of the ring-1 neighbours).  du never goes to memory.  Same expressions in the same
 // order as k_tile_cheb + k_tile_flux_limit => bitwise the same step.  Latency regime only.
 // (LEAN = 1 compiles to 72 VGPRs when left alone; the waves-per-SIMD bound 8 holds it at the 64 of LEAN = 0, without scratch)
-template <int GEOM, int LEAN>
-__global__ void __launch_bounds__(STRIP_T, LEAN ? 8 : 1)
+// PL (FEMFCT_TILE_FIT): the patch edge.  32 is the 8 x 8 tile; 30 is a 6 x 6 tile whose halo of 12 needs no more -- 15
+// waves instead of 16 and more workgroups, chosen while each still gets a compute unit (femfct_tile_fit).  The block is
+// PL^2 threads rounded up to whole waves; the spare threads own no node (tile_geom).
+template <int GEOM, int LEAN, int PL>
+__global__ void __launch_bounds__((PL * PL + WAVE - 1) / WAVE * WAVE, (LEAN && PL == TILE_L) ? 8 : 1)
 k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, const double* __restrict__ b_,
                        const double* __restrict__ ymid_, const double* __restrict__ yold_, int K, CheOmegas om,
                        double md_scale, MatRef D_ref, const double* __restrict__ ulow_,
                        const double* __restrict__ ml, double dt, VecRef out_ref, int64_t out_bstride, EndArgs e) {
-    constexpr int W = 7, HH = 12;
-    __shared__ double ys[LEAN ? 2 : 3][TILE_L * TILE_LD];
-    __shared__ double su[TILE_L * TILE_LD], srp[TILE_L * TILE_LD], srm[TILE_L * TILE_LD];
+    constexpr int W = 7, HH = 12, PLD = PL + 1;
+    constexpr bool CONE = LEAN == 2;
+    static_assert(PL == TILE_L || LEAN, "fitted patches run the lean loops only");
+    __shared__ double ys[LEAN ? 2 : 3][PL * PLD];
+    __shared__ double su[PL * PLD], srp[PL * PLD], srm[PL * PLD];
     const int bz = blockIdx.z;
     const int64_t voff = (int64_t)bz * n;
     const double* D_ = mat_ptr(D_ref, bz);     // the step's D (one of the pre-built sequence, or the workspace's)
-    const TileGeom g = tile_geom<TILE_L - 2 * HH, HH>(N);
+    TILE_STAMP_BEGIN();
+    const TileGeom g = tile_geom<PL - 2 * HH, HH, PL>(N);
     double mv[W - 1], dv[W - 1], md = 1.0, rmd = 1.0, bv = 0.0, ym = 0.0, yo = 0.0, ui = 0.0, mli = 1.0;
 #pragma unroll
     for (int s = 0; s < W - 1; ++s) { mv[s] = 0.0; dv[s] = 0.0; }
-    if (g.inside) {
+    [[maybe_unused]] bool flux_node = false;
+    if constexpr (CONE) {
+        // the mass row, the rhs and y_old where the node iterates or takes fluxes (`have` and `klive` below), y_mid where
+        // an iterating node or a flux reads it, u_L and M_L two rings out (the fluxes and their neighbours), D on the first ring
+        const int dist = tile_hexdist<HH, PL>(g);
+        flux_node = g.inside && g.kvalid >= K + 1 && dist <= 1;
+        if (g.inside && (min(g.kvalid, K - max(dist - 2, 0)) > 0 || flux_node)) {
+            md = M[g.i];
+            rmd = 1.0 / (md_scale * md);
+            if (GEOM) {
+                const int pc = mass_edge_counts(g.gx, g.gy, N - 1);
+                const double mq = (0.5 * h * h) / 12.0;
+#pragma unroll
+                for (int s = 1; s < W; ++s) mv[s - 1] = (double)((pc >> (2 * (s - 1))) & 3) * mq;
+            } else {
+#pragma unroll
+                for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+            }
+            bv = b_[voff + g.i];
+            yo = yold_[voff + g.i];
+        }
+        if (g.inside && max(dist - 2, 0) <= K) ym = ymid_[voff + g.i];
+        if (g.inside && dist <= 2) {
+            ui = ulow_[voff + g.i];
+            mli = ml[g.i];
+        }
+    } else if (g.inside) {
         md = M[g.i];
         rmd = 1.0 / (md_scale * md);
         if (GEOM) {
@@ -729,16 +867,19 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         ui = ulow_[voff + g.i];
         mli = ml[g.i];
     }
-    ys[0][g.self] = LEAN ? ym : yo;        // LEAN: both buffers hold y_mid, the node's own y_mid / y_old stay in ym, yo
-    ys[1][g.self] = ym;
-    su[g.self] = ui;
-    srp[g.self] = 1.0;
-    srm[g.self] = 1.0;
+    if (!tile_spare<PL>()) {
+        ys[0][g.self] = LEAN ? ym : yo;    // LEAN: both buffers hold y_mid, the node's own y_mid / y_old stay in ym, yo
+        ys[1][g.self] = ym;
+        su[g.self] = ui;
+        srp[g.self] = 1.0;
+        srm[g.self] = 1.0;
+    }
     __syncthreads();
+    TILE_STAMP_LOADED();
     step_log_early(e);        // (behind this kernel's own loads; its round trip is covered by the Chebyshev iterations)
     // D is first needed by the fluxes: requested behind the log copy (which waits for every load in flight) so that a
     // pre-built D_k, an HBM round trip behind the level counter, is covered by the iterations too
-    if (g.inside) {
+    if (g.inside && (!CONE || flux_node)) {
 #pragma unroll
         for (int s = 1; s < W; ++s) dv[s - 1] = D_[(int64_t)s * n + g.i];
     }
@@ -746,17 +887,17 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
     // fluxes where all six neighbours carry the final du (one ring inside the iterations' validity).  LEAN: only where
     // the owned tile reads R+- (its first ring); there the node and its six neighbours iterated to the end (their
     // kvalid is at least K), so the last buffer holds their final du.
-    const bool have = g.inside && g.kvalid >= K + 1 && (!LEAN || tile_dist<HH>(g) <= 1);
+    const bool have = g.inside && g.kvalid >= K + 1 && (!LEAN || lean_dist<HH, LEAN, PL>(g) <= 1);
     if constexpr (LEAN) {
         // the fluxes of the tile's first ring need du two rings out: a node stops iterating d - 2 iterations early
-        const int klive = min(g.kvalid, K - max(tile_dist<HH>(g) - 2, 0));
-        const LeanAddr a = lean_addr(ys, g);
+        const int klive = min(g.kvalid, K - max(lean_dist<HH, LEAN, PL>(g) - 2, 0));
+        const LeanAddr a = lean_addr<PL>(ys, g);
         int k = 0;
         for (; k + 1 < K; k += 2) {
-            lean_cheb_iter<0>(a, k < klive, mv, md, rmd, bv, om.w[k], ym, yo);
-            lean_cheb_iter<1>(a, k + 1 < klive, mv, md, rmd, bv, om.w[k + 1], ym, yo);
+            lean_cheb_iter<0, PL>(a, k < klive, mv, md, rmd, bv, om.w[k], ym, yo);
+            lean_cheb_iter<1, PL>(a, k + 1 < klive, mv, md, rmd, bv, om.w[k + 1], ym, yo);
         }
-        if (k < K) lean_cheb_iter<0>(a, k < klive, mv, md, rmd, bv, om.w[k], ym, yo);
+        if (k < K) lean_cheb_iter<0, PL>(a, k < klive, mv, md, rmd, bv, om.w[k], ym, yo);
         im = K & 1;                         // the buffer iteration K - 1 wrote (K = 0: either)
     } else
     for (int k = 0; k < K; ++k) {
@@ -809,6 +950,7 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         double* out = const_cast<double*>(vec_ptr(out_ref)) + bz * out_bstride;
         out[g.i] = ui + dt * fbar / mli;
     }
+    TILE_STAMP_END(3);
     step_end_by_last_workgroup(e);
 }
 
@@ -816,16 +958,20 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
 //   r = rhs - A u_L (helpers.py:1814), y_1 = w_1 r / Md, then iterations 2..K+1 (helpers.py:175-184).
 // 12 x 12 tile + halo 10: one ring is spent on A u_L, nine on Chebyshev iterations 2..10.
 // Also finalises the low-order solve's bookkeeping (what k_dudt_rhs does in the unfused sequence).
-template <int LEAN>
-__global__ void __launch_bounds__(STRIP_T)
-k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride,
+// GEOM: the off-diagonals of the mesh's own mass matrix from the cell geometry (as k_tile_cheb_flux_limit) instead of
+// six loads per node.  PL (FEMFCT_TILE_FIT): patch edge 32 (12 x 12 tile) or 26 (6 x 6 tile, 11 waves: femfct_tile_fit).
+template <int LEAN, int GEOM, int PL>
+__global__ void __launch_bounds__((PL * PL + WAVE - 1) / WAVE * WAVE)
+k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride,
                  const double* __restrict__ M, const double* __restrict__ xa_, const double* __restrict__ xb_,
                  double* __restrict__ ulow_, double* __restrict__ rdu_, double* __restrict__ omid_,
                  double* __restrict__ oold_, double* __restrict__ part, StepCtl* __restrict__ ctl_, int budget,
                  int part_count, int iters_per_unit, double rel_tol, const double* __restrict__ partk, int exact_k,
                  int K, CheOmegas om, double md_scale, double omega1) {
-    constexpr int W = 7, H = 10;
-    __shared__ double ys[LEAN ? 2 : 3][TILE_L * TILE_LD];
+    constexpr int W = 7, H = 10, PLD = PL + 1;
+    constexpr bool CONE = LEAN == 2;
+    static_assert(PL == TILE_L || LEAN, "fitted patches run the lean loops only");
+    __shared__ double ys[LEAN ? 2 : 3][PL * PLD];
     __shared__ double smem[64];
     const int bz = blockIdx.z;
     StepCtl* ctl = ctl_ + bz;
@@ -851,28 +997,62 @@ k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride
     const double* x = (parity ? xb_ : xa_) + voff;
     const double* rhs = vec_ptr(rhs_ref);
     if (rhs) rhs += bz * rhs_bstride;
-    const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
+    TILE_STAMP_BEGIN();
+    const TileGeom g = tile_geom<PL - 2 * H, H, PL>(N);
     double av[W], mv[W - 1], md = 1.0, rmd = 1.0, ui = 0.0, ri = 0.0;
 #pragma unroll
     for (int s = 0; s < W; ++s) av[s] = 0.0;
 #pragma unroll
     for (int s = 0; s < W - 1; ++s) mv[s] = 0.0;
-    if (g.inside) {
+    bool need_r = g.kvalid >= 1;            // r = rhs - A u_L on every node whose neighbours are in the patch
+    if constexpr (CONE) {
+        // r and y_1 only where an iterating node reads y_1 (d <= K): there the row of A, the rhs and the diagonal of M;
+        // the off-diagonals of M where the node iterates at all (d < K); u_L one ring further out than r
+        const int dist = tile_hexdist<H, PL>(g);
+        need_r = need_r && dist <= K;
+        if (g.inside && need_r) {
+            md = M[g.i];
+            rmd = 1.0 / (md_scale * md);
+#pragma unroll
+            for (int s = 0; s < W; ++s) av[s] = A[(int64_t)s * n + g.i];
+            ri = rhs ? rhs[g.i] : 0.0;
+        }
+        if (g.inside && g.kvalid > 1 && dist < K) {
+            if (GEOM) {
+                const int pc = mass_edge_counts(g.gx, g.gy, N - 1);
+                const double mq = (0.5 * h * h) / 12.0;
+#pragma unroll
+                for (int s = 1; s < W; ++s) mv[s - 1] = (double)((pc >> (2 * (s - 1))) & 3) * mq;
+            } else {
+#pragma unroll
+                for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+            }
+        }
+        if (g.inside && dist <= K + 1) ui = x[g.i];
+    } else if (g.inside) {
         md = M[g.i];
         rmd = 1.0 / (md_scale * md);
 #pragma unroll
         for (int s = 0; s < W; ++s) av[s] = A[(int64_t)s * n + g.i];
+        if (GEOM) {
+            const int pc = mass_edge_counts(g.gx, g.gy, N - 1);
+            const double mq = (0.5 * h * h) / 12.0;
 #pragma unroll
-        for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+            for (int s = 1; s < W; ++s) mv[s - 1] = (double)((pc >> (2 * (s - 1))) & 3) * mq;
+        } else {
+#pragma unroll
+            for (int s = 1; s < W; ++s) mv[s - 1] = M[(int64_t)s * n + g.i];
+        }
         ui = x[g.i];
         ri = rhs ? rhs[g.i] : 0.0;
     }
     constexpr int UB = LEAN ? 0 : 2;        // the buffer u_L is staged in
-    ys[UB][g.self] = ui;
+    const bool spare = tile_spare<PL>();
+    if (!spare) ys[UB][g.self] = ui;
     __syncthreads();
-    // r = rhs - A u_L on every node whose neighbours are in the patch
+    TILE_STAMP_LOADED();
     double r = 0.0, y1 = 0.0;
-    if (g.kvalid >= 1) {
+    if (need_r) {
         double acc = av[0] * ui;
 #pragma unroll
         for (int s = 1; s < W; ++s) acc = fma(av[s], ys[UB][g.nb[s - 1]], acc);
@@ -882,25 +1062,26 @@ k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride
     if constexpr (LEAN) {
         // both buffers hold y_mid = y_1 (buffer 1 first: buffer 0 is still being read as u_L); y_mid and y_old of the
         // node itself stay in registers.  Iteration 0 reads buffer 1.
-        ys[1][g.self] = y1;
+        if (!spare) ys[1][g.self] = y1;
         __syncthreads();
-        ys[0][g.self] = y1;                 // (own slot only, rewritten by this thread alone before anyone reads it)
+        if (!spare) ys[0][g.self] = y1;     // (own slot only, rewritten by this thread alone before anyone reads it)
         double ym = y1, yo = 0.0;
-        const int dist = tile_dist<H>(g);
-        const LeanAddr a = lean_addr(ys, g);
+        const int dist = lean_dist<H, LEAN, PL>(g);
+        const LeanAddr a = lean_addr<PL>(ys, g);
         auto live = [&](int k) { return k + 1 < g.kvalid && k < K - dist; };   // one ring already spent on A u_L
         int k = 0;
         for (; k + 1 < K; k += 2) {
-            lean_cheb_iter<1>(a, live(k), mv, md, rmd, r, om.w[k], ym, yo);
-            lean_cheb_iter<0>(a, live(k + 1), mv, md, rmd, r, om.w[k + 1], ym, yo);
+            lean_cheb_iter<1, PL>(a, live(k), mv, md, rmd, r, om.w[k], ym, yo);
+            lean_cheb_iter<0, PL>(a, live(k + 1), mv, md, rmd, r, om.w[k + 1], ym, yo);
         }
-        if (k < K) lean_cheb_iter<1>(a, live(k), mv, md, rmd, r, om.w[k], ym, yo);
+        if (k < K) lean_cheb_iter<1, PL>(a, live(k), mv, md, rmd, r, om.w[k], ym, yo);
         if (g.owned) {
             ulow_[voff + g.i] = ui;
             rdu_[voff + g.i] = r;
             omid_[voff + g.i] = ym;
             if (oold_) oold_[voff + g.i] = yo;
         }
+        TILE_STAMP_END(2);
         return;
     }
     __syncthreads();
@@ -930,11 +1111,33 @@ k_tile_dudt_cheb(int n, int N, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride
         omid_[voff + g.i] = ys[im][g.self];
         if (oold_) oold_[voff + g.i] = ys[io][g.self];
     }
+    TILE_STAMP_END(2);
 }
 
 }  // namespace
 
+#ifdef FEMFCT_TUNING
+// appends the phase sums since the last dump to `path` (one line per kernel) and clears them
+void femfct_tile_phase_dump(const char* path) {
+    static const char* names[4] = {"k_tile_build_jacobi", "k_tile_jacobi", "k_tile_dudt_cheb", "k_tile_cheb_flux_limit"};
+    unsigned long long h[4][4];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile_phase), sizeof(h)) != hipSuccess) return;
+    if (FILE* f = fopen(path, "a")) {
+        for (int k = 0; k < 4; ++k)
+            if (h[k][2])
+                fprintf(f, "%-24s launches %8llu  load phase %7.3f us  whole kernel %7.3f us  share %5.1f %%\n", names[k], h[k][2],
+                        0.01 * h[k][0] / h[k][2], 0.01 * h[k][1] / h[k][2], 100.0 * h[k][0] / (double)h[k][1]);
+        fclose(f);
+    }
+    memset(h, 0, sizeof(h));
+    hipMemcpyToSymbol(HIP_SYMBOL(g_tile_phase), h, sizeof(h));
+}
+#endif
+
 // ---- launchers, in the order of a step ---------------------------------------------------------------
+
+// the LEAN template argument: 0 the loops as they were, 1 the lean loops, 2 the lean loops on the hexagonal cone
+static int tile_lean_mode(const femfct_ctx* ctx) { return ctx->tile_lean ? (ctx->tile_cone ? 2 : 1) : 0; }
 
 // launch 0 with the operator construction fused in (latency regime; needs >= 2 launches in total because
 // ||b|| is reduced by launch 1).  Later launches: femfct_enqueue_tile_jacobi(..., bn_launch = 1, g_build = tiles^2).
@@ -951,7 +1154,7 @@ int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, MatRef
     };
     with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
         constexpr int H = decltype(h)::value;
-        with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+        with_constant<0, 2>(tile_lean_mode(ctx), [&](auto l) {
             constexpr int LEAN = decltype(l)::value;
             if (pre) go(k_tile_build_jacobi<H, 1, LEAN>); else go(k_tile_build_jacobi<H, 0, LEAN>);
         });
@@ -982,7 +1185,7 @@ int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double
         hipLaunchKernelGGL(kernel, grid, dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, L, b, xa, xb, ctx->d_part, ctx->d_ctl,
                            launch, pl.K, g_build, ctx->rel_tol, bigp, pk, bn_launch, defer_arg);
     };
-    with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+    with_constant<0, 2>(tile_lean_mode(ctx), [&](auto l) {
         constexpr int LEAN = decltype(l)::value;
         if (big) {
             go(k_tile_jacobi<8, 0, 1, LEAN>, 0);
@@ -1012,6 +1215,8 @@ int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, MatRef A, VecRef rhs, int64_t
                                   const double* omegas, double md_scale, int32_t batch, int* tail_first) {
     constexpr int H = 10;
     const int T = TILE_L - 2 * H, t = (ctx->N + T - 1) / T;
+    const bool fit = femfct_tile_fit(ctx, batch);
+    const int tl = fit ? (ctx->N + 5) / 6 : t;           // workgroups per side of this launch (the chained ones keep T = 12)
     const int K = std::min(iters - 1, H - 1);            // iterations 2..K+1 here
     CheOmegas om;
     for (int k = 0; k < K; ++k) om.w[k] = omegas[k + 1];
@@ -1019,11 +1224,22 @@ int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, MatRef A, VecRef rhs, int64_t
     double* omid = last ? ctx->d_du : ctx->d_y0;
     double* oold = last ? nullptr : ctx->d_y2;
     femfct_prof_begin(ctx, KC_DUDT_RHS);
-    with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
-        hipLaunchKernelGGL(k_tile_dudt_cheb<decltype(l)::value>, dim3(t, exact_k < 0 ? t + 1 : t, batch), dim3(STRIP_T), 0,
-                           ctx->stream, ctx->n, ctx->N, A, rhs, rhs_bstride, ctx->d_M, ctx->d_xa, ctx->d_xb, ulow, ctx->d_rdu, omid,
-                           oold, ctx->d_part, ctx->d_ctl, budget_units, part_count, iters_per_unit, ctx->rel_tol,
+    auto go = [&](auto kernel, int PL) {
+        hipLaunchKernelGGL(kernel, dim3(tl, exact_k < 0 ? tl + 1 : tl, batch), dim3((PL * PL + WAVE - 1) / WAVE * WAVE), 0,
+                           ctx->stream, ctx->n, ctx->N, ctx->h, A, rhs, rhs_bstride, ctx->d_M, ctx->d_xa, ctx->d_xb, ulow, ctx->d_rdu,
+                           omid, oold, ctx->d_part, ctx->d_ctl, budget_units, part_count, iters_per_unit, ctx->rel_tol,
                            exact_k ? ctx->d_partk : nullptr, exact_k, K, om, md_scale, omegas[0]);
+    };
+    // (the mass row from the geometry rides with the lean loops: FEMFCT_TILE_LEAN=0 is the kernel as it was)
+    with_constant<0, 1>(ctx->tile_lean && femfct_geom_mass(ctx), [&](auto gm) {
+        constexpr int GM = decltype(gm)::value;
+        if (fit) {
+            if (ctx->tile_cone) go(k_tile_dudt_cheb<2, GM, 26>, 26); else go(k_tile_dudt_cheb<1, GM, 26>, 26);
+        } else if constexpr (GM) {
+            if (ctx->tile_cone) go(k_tile_dudt_cheb<2, 1, TILE_L>, TILE_L); else go(k_tile_dudt_cheb<1, 1, TILE_L>, TILE_L);
+        } else {
+            with_constant<0, 2>(tile_lean_mode(ctx), [&](auto l) { go(k_tile_dudt_cheb<decltype(l)::value, 0, TILE_L>, TILE_L); });
+        }
     });
     femfct_prof_end(ctx);
     if (tail_first) *tail_first = last ? 0 : K + 2;
@@ -1050,7 +1266,7 @@ int femfct_enqueue_tile_cheb(femfct_ctx* ctx, const TilePlan& pl, const double* 
         if (io_in && k0 == k_first) { io.mid_ref = io_in->mid_ref; io.mid_bs = io_in->mid_bs; }
         if (io_in && k1 == k_last + 1) { io.out_ref = io_in->out_ref; io.out_bs = io_in->out_bs; }
         with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
-            with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
+            with_constant<0, 2>(tile_lean_mode(ctx), [&](auto l) {
                 hipLaunchKernelGGL((k_tile_cheb<decltype(h)::value, decltype(l)::value>), dim3(pl.tiles, pl.tiles, batch),
                                    dim3(STRIP_T), 0, ctx->stream, ctx->n, ctx->N, ctx->d_M, b, mid, old, omid, oold, k1 - k0, om,
                                    md_scale, io);
@@ -1083,14 +1299,20 @@ int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const 
     const EndArgs e = step_end_args(ctx, batch, fuse_end);
     CheOmegas om;
     for (int k = k_first; k <= k_last; ++k) om.w[k - k_first] = omegas[k - 1];
-    const int t = (ctx->N + 7) / 8;
+    const bool fit = femfct_tile_fit(ctx, batch);
+    const int t = fit ? (ctx->N + 5) / 6 : (ctx->N + 7) / 8;
     femfct_prof_begin(ctx, KC_FLUX);
+    auto go = [&](auto kernel, int PL) {
+        hipLaunchKernelGGL(kernel, dim3(t, t, batch), dim3((PL * PL + WAVE - 1) / WAVE * WAVE), 0, ctx->stream, ctx->n, ctx->N,
+                           ctx->h, ctx->d_M, b, in_mid, in_old, K, om, md_scale, D, ulow, ctx->d_ml, dt, out, out_bstride, e);
+    };
     with_constant<0, 1>(femfct_geom_mass(ctx), [&](auto gm) {
-        with_constant<0, 1>(ctx->tile_lean, [&](auto l) {
-            hipLaunchKernelGGL((k_tile_cheb_flux_limit<decltype(gm)::value, decltype(l)::value>), dim3(t, t, batch), dim3(STRIP_T),
-                               0, ctx->stream, ctx->n, ctx->N, ctx->h, ctx->d_M, b, in_mid, in_old, K, om, md_scale, D, ulow,
-                               ctx->d_ml, dt, out, out_bstride, e);
-        });
+        constexpr int GM = decltype(gm)::value;
+        if (fit) {
+            if (ctx->tile_cone) go(k_tile_cheb_flux_limit<GM, 2, 30>, 30); else go(k_tile_cheb_flux_limit<GM, 1, 30>, 30);
+        } else {
+            with_constant<0, 2>(tile_lean_mode(ctx), [&](auto l) { go(k_tile_cheb_flux_limit<GM, decltype(l)::value, TILE_L>, TILE_L); });
+        }
     });
     femfct_prof_end(ctx);
     return FEMFCT_OK;
@@ -1131,6 +1353,15 @@ bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch) {
     if (!ctx->fuse_flux || ctx->N > 512) return false;
     const int t = (ctx->N + 7) / 8;
     return (int64_t)t * t * batch <= ctx->wg_slots;
+}
+
+// Fitted patches of the fused du/dt and limiter launches (FEMFCT_TILE_FIT): 6 x 6 tiles, whose halos of 10 and 12 need
+// patches of 26 and 30 nodes per side only (11 and 15 waves, a third fewer loads in the du/dt launch), while every
+// workgroup -- the extra row of the deferred test included -- still gets a compute unit of its own.  Lean loops only.
+bool femfct_tile_fit(const femfct_ctx* ctx, int32_t batch) {
+    if (!ctx->tile_lean || !ctx->tile_fit) return false;
+    const int t = (ctx->N + 5) / 6;
+    return (int64_t)t * (t + 1) * batch <= ctx->wg_slots;
 }
 
 // The 32 x 32 patch is split as tile + 2 halos with halo H in {8, 9, 10}: H sweeps fit in one launch.
