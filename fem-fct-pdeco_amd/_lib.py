@@ -126,6 +126,11 @@ SIGNATURES = {
     "femfct_chtxs_adjoint_obs": (C.c_int, [_p, _p, _p, _p, _p, _p, _d, _p, _d, _p, _p, _p, _p, _i, _d, _p, _d, _p, _i, _i]),
     "femfct_obs_load": (C.c_int, [_p, _p, _p, _p, _i, _d, _p, _p, _i]),
     "femfct_obs_cost": (C.c_int, [_p, _p, _p, _p, _p, _i, _i, _p]),
+    "femfct_solidbody_adjoint_bounds": (C.c_int, [_p, _p, _p, _i, _p, _p, _p, _d, _p, _p, _p, _d, _p, _p, _p, _i, _d, _d, _d,
+                                                  _d, _d, _i]),
+    "femfct_linear_adjoint_react_bounds": (C.c_int, [_p, _p, _p, _p, _p, _p, _d, _p, _p, _p, _d, _p, _p, _p, _i, _d, _d, _i]),
+    "femfct_bound_load": (C.c_int, [_p, _p, _p, _p, _p, _i, _d, _p, _p, _p, _p, _p, _d, _p, _p, _i]),
+    "femfct_bound_cost": (C.c_int, [_p, _p, _p, _p, _p, _d, _p, _i, _i, _p]),
     "femfct_assemble_weighted_mass": (C.c_int, [_p, _p, _p]),
     "femfct_traj_info": (C.c_int, [_p, C.POINTER(StepInfo), _i, _i]),
     "femfct_descent_pointwise": (C.c_int, [_p, C.c_int64, _d, _p, _d, _p, _p, _d, _p]),

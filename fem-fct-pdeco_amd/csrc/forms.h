@@ -46,6 +46,17 @@ struct ObsLoadSpec {
     double dt = 1.0;
 };
 
+// State bounds lo <= u <= hi as a Moreau-Yosida penalty (kernels_bounds.hip): what the load of an adjoint step loses,
+//   (sigma/dt) * gamma * ml_i * ws_i * v_i,    v = u - clip(u, lo, hi),
+// sigma: the level's weight, read on the device; sigma == 0: u is not read.  lo / hi absent: no bound on that side; ws
+// (a nodal window) absent: 1.  lo, hi, ml, ws are shared by the batch.
+struct BoundSpec {
+    VecRef sigma{nullptr, nullptr, 0, 0}, u{nullptr, nullptr, 0, 0};
+    int64_t u_bs = 0;
+    const double *lo = nullptr, *hi = nullptr, *ml = nullptr, *ws = nullptr;
+    double gamma = 0.0;
+};
+
 // out_i = s1 * int q1 q2 phi_i + s2*(da_i - db_i) + int (g0 + g1*a + g2*a^2) a^e b phi_i   (kernels_growth.hip: the growth
 // term of the chemotaxis system; b absent: 1, q1 / da absent: no such term)
 struct GrowthLoadSpec {
@@ -107,6 +118,12 @@ int femfct_enqueue_react_load(femfct_ctx* ctx, const ReactLoadSpec& sp, double* 
 int femfct_enqueue_obs_load(femfct_ctx* ctx, const ObsLoadSpec& sp, double* out, int32_t batch);
 int femfct_enqueue_obs_terminal(femfct_ctx* ctx, double tau, const double* window, const double* uhat, int64_t uhat_bs,
                                 const double* u, int64_t u_bs, double* p, int64_t p_bs, int32_t batch);
+// the snapshot load minus the penalty term of the state bounds, one launch; the terminal condition with its penalty part,
+// p_Nt = tau ws_obs (uhat - u) - sigma[0] gamma ws .* v (sigma: a device pointer to the level's weight)
+int femfct_enqueue_bound_load(femfct_ctx* ctx, const ObsLoadSpec& sp, const BoundSpec& bs, double* out, int32_t batch);
+int femfct_enqueue_bound_terminal(femfct_ctx* ctx, double tau, const double* window, const double* uhat, int64_t uhat_bs,
+                                  const double* u, int64_t u_bs, const double* sigma, double gamma, const double* lo,
+                                  const double* hi, const double* ws, double* p, int64_t p_bs, int32_t batch);
 int femfct_enqueue_chtxs_matrix(femfct_ctx* ctx, int adjoint, VecRef u, int64_t u_bs, VecRef v, int64_t v_bs,
                                 double Dm, double chi, double eta, double* out, int32_t batch);
 int femfct_enqueue_growth_load(femfct_ctx* ctx, const GrowthLoadSpec& sp, double* out, int32_t batch);

@@ -22,70 +22,27 @@
 #include "forms.h"
 #include "solidbody_op.h"
 #include "obs_device.h"
+#include "obs_load_device.h"
 
 #include <algorithm>
 
 namespace {
-
-__device__ __forceinline__ const double* member(const VecRef& r, int64_t bstride, int bz) {
-    const double* p = vec_ptr(r);
-    return p ? p + bz * bstride : nullptr;
-}
-
-// (Mf(f) x)_P with the nodal values of f and x on the stencil of P (slot 0 = P)
-__device__ __forceinline__ double weighted_mass_row(const NodeXY& P, int nc, double k60, const double* fv, const double* xv) {
-    double r = 0.0;
-    for_each_tri(P, nc, [&](const TriInfo& T, int, int) {
-        const double t = p1_triple_term(T, fv, xv);
-        r += k60 * t;
-    });
-    return r;
-}
 
 __global__ void k_obs_load(MeshArgs m, ObsLoadSpec sp, double* __restrict__ out_) {
     const int bz = blockIdx.y, n = m.n;
     const double th = *vec_ptr(sp.theta);       // the level's weight: one value for the whole grid
     const bool observed = th != 0.0;
     const double scale = th / sp.dt;
-    const double* a = observed ? member(sp.a, sp.a_bs, bz) : nullptr;
-    const double* b = observed ? member(sp.b, sp.b_bs, bz) : nullptr;
+    const double* a = observed ? obs_member(sp.a, sp.a_bs, bz) : nullptr;
+    const double* b = observed ? obs_member(sp.b, sp.b_bs, bz) : nullptr;
     const double* w = vec_ptr(sp.w);            // window, may be absent: Mw = M
-    const double* g = member(sp.g, 0, bz);      // reaction coefficient, may be absent: no Mg(g) x term
-    const double* x = member(sp.x, sp.x_bs, bz);
+    const double* g = obs_member(sp.g, 0, bz);      // reaction coefficient, may be absent: no Mg(g) x term
+    const double* x = obs_member(sp.x, sp.x_bs, bz);
     double* out = out_ + (int64_t)bz * n;
     const double k60 = 0.5 * m.h * m.h / 60.0;
     RowRange rr = block_rows(n);
     for (int i = rr.begin + threadIdx.x; i < rr.end; i += blockDim.x) {
-        double acc = 0.0;
-        if (observed && !w) {
-            acc = m.M[i] * (a[i] - b[i]);
-#pragma unroll
-            for (int s = 1; s < STENCIL_W; ++s) {
-                const int64_t idx = (int64_t)s * n + i;
-                const int j = m.cols[idx];
-                acc += m.M[idx] * (a[j] - b[j]);
-            }
-            acc = scale * acc;
-        } else if (observed) {
-            double wv[STENCIL_W], dv[STENCIL_W];
-            wv[0] = w[i]; dv[0] = a[i] - b[i];
-#pragma unroll
-            for (int s = 1; s < STENCIL_W; ++s) {
-                const int j = m.cols[(int64_t)s * n + i];
-                wv[s] = w[j]; dv[s] = a[j] - b[j];
-            }
-            acc = scale * weighted_mass_row(node_xy(i, m.d2v, m.N), m.nc, k60, wv, dv);
-        }
-        if (g) {
-            double gv[STENCIL_W], xv[STENCIL_W];
-            gv[0] = g[i]; xv[0] = x[i];
-#pragma unroll
-            for (int s = 1; s < STENCIL_W; ++s) {
-                const int j = m.cols[(int64_t)s * n + i];
-                gv[s] = g[j]; xv[s] = x[j];
-            }
-            acc = acc - weighted_mass_row(node_xy(i, m.d2v, m.N), m.nc, k60, gv, xv);
-        }
+        OBS_LOAD_ROW(acc)       // reads m, n, i, k60, observed, scale, a, b, w, g, x by name (obs_load_device.h)
         out[i] = acc;
     }
 }
@@ -129,7 +86,7 @@ __global__ void __launch_bounds__(256) k_obs_cost_part(MeshArgs m, const double*
                 wv[s] = w ? w[j] : 1.0;
                 r += m.M[idx] * dv[s];
             }
-            if (w) r = weighted_mass_row(node_xy(i, m.d2v, m.N), m.nc, k60, wv, dv);
+            if (w) r = obs_weighted_mass_row(node_xy(i, m.d2v, m.N), m.nc, k60, wv, dv);
             sum += wt * (dv[0] * r);
         }
     }

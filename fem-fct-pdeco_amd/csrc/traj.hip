@@ -16,6 +16,7 @@
 #include "solidbody_op.h"
 
 #include <algorithm>
+#include <cmath>
 
 int femfct_enqueue_step_ref(femfct_ctx* ctx, const double* A, const double* N, int32_t nshared, VecRef rhs,
                             int64_t rhs_bstride, VecRef u_n, int64_t u_bstride, double dt, VecRef u_out,
@@ -249,6 +250,14 @@ struct ObsArgs {
     const double* window;
 };
 
+// State bounds as a Moreau-Yosida penalty on top of the tracking (kernels_bounds.hip; needs obs): lower / upper (either
+// may be null) and window_s: n doubles on the device, sigma: num_steps + 1 level weights on the device.
+struct BoundArgs {
+    const double *lower, *upper;
+    double gamma;
+    const double *sigma, *window_s;
+};
+
 // g_traj (may be null): rhs_n = [M (uhat_n - u_n)] - Mg(g_n) p_{n+1}, the coefficient at the level being produced
 // (advection_FCT_PDECO_finaltime_exact.py:317-321); the final-time sweep has a right-hand side then, too
 // obs (may be null; `alltime` is unused with it): uhat is a trajectory, p_Nt = tau omega (uhat_Nt - u_Nt) and
@@ -256,12 +265,17 @@ struct ObsArgs {
 static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
                                    const double* g_traj, const double* u_traj, const double* uhat, double* p_traj,
                                    int32_t num_steps, double dt, double eps, double rot_scale, double bx, double by,
-                                   int32_t alltime, int32_t batch, const ObsArgs* obs = nullptr) {
+                                   int32_t alltime, int32_t batch, const ObsArgs* obs = nullptr,
+                                   const BoundArgs* bnd = nullptr) {
     FEMFCT_ENTER(ctx);
     ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
     ARG_TRY(ctx, c_traj && u_traj && uhat && p_traj && num_steps >= 1 && dt > 0 && batch >= 1, "bad argument");
     ARG_TRY(ctx, !obs || obs->theta, "theta is null");
     ARG_TRY(ctx, !obs || obs->tau >= 0.0, "tau must be >= 0");
+    ARG_TRY(ctx, !bnd || obs, "state bounds need observations");
+    ARG_TRY(ctx, !bnd || bnd->sigma, "sigma is null");
+    ARG_TRY(ctx, !bnd || bnd->lower || bnd->upper, "no bound: lower and upper are both null");
+    ARG_TRY(ctx, !bnd || (bnd->gamma >= 0.0 && std::isfinite(bnd->gamma)), "gamma must be finite and >= 0");
     ARG_TRY(ctx, Arot_ell || rot_scale == 0.0, "Arot_ell is required when rot_scale != 0");
     int rc = femfct_ensure_traj_ws(ctx, batch, num_steps);
     if (rc != FEMFCT_OK) return rc;
@@ -284,7 +298,11 @@ static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, cons
         // terminal condition: p(T) = uhat_T - u(T) (finaltime.py:201) or 0 (alltime.py:232)
         if (obs) {      // p(T) = tau omega (uhat_T - u(T)); tau = 0: uhat_T is not read
             double* pT = p_traj + (int64_t)num_steps * n;
-            if (obs->tau == 0.0)
+            if (bnd)    // ... - sigma_Nt gamma window_s .* v_Nt
+                femfct_enqueue_bound_terminal(ctx, obs->tau, obs->window, uhat + (int64_t)num_steps * n, tstride,
+                                              u_traj + (int64_t)num_steps * n, tstride, bnd->sigma + num_steps, bnd->gamma,
+                                              bnd->lower, bnd->upper, bnd->window_s, pT, tstride, batch);
+            else if (obs->tau == 0.0)
                 for (int32_t b = 0; b < batch; ++b) HIP_TRY(ctx, hipMemsetAsync(pT + b * tstride, 0, sizeof(double) * n, ctx->stream));
             else
                 femfct_enqueue_obs_terminal(ctx, obs->tau, obs->window, uhat + (int64_t)num_steps * n, tstride,
@@ -310,6 +328,14 @@ static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, cons
             key.push_back(key_bits(obs->window));
             key.push_back(key_bits((int32_t)1));
         }
+        if (bnd) {      // the load kernel with the penalty term: its arguments are baked into the graph, gamma too
+            key.push_back(key_bits(bnd->lower));
+            key.push_back(key_bits(bnd->upper));
+            key.push_back(key_bits(bnd->gamma));
+            key.push_back(key_bits(bnd->sigma));
+            key.push_back(key_bits(bnd->window_s));
+            key.push_back(key_bits((int32_t)2));
+        }
         return femfct_run_graph_reps(ctx, key, reps, -1, [&]() {
             // level counter = n: control c_n (finaltime.py:213), p_{n+1} -> p_n
             MatRef A = Aall;
@@ -333,7 +359,16 @@ static int solidbody_adjoint_sweep(femfct_ctx* ctx, const double* Arot_ell, cons
                     ol.g = lref(ctx, g_traj, lv, n, 0);
                     ol.x = lref(ctx, p_traj, lv, n, 1); ol.x_bs = tstride;
                 }
-                femfct_enqueue_obs_load(ctx, ol, ctx->d_trRhs, batch);
+                if (bnd) {
+                    BoundSpec bs;
+                    bs.sigma = lref(ctx, bnd->sigma, lv, 1, 0);
+                    bs.u = lref(ctx, u_traj, lv, n, 0); bs.u_bs = tstride;
+                    bs.lo = bnd->lower; bs.hi = bnd->upper; bs.ml = ctx->d_ml; bs.ws = bnd->window_s;
+                    bs.gamma = bnd->gamma;
+                    femfct_enqueue_bound_load(ctx, ol, bs, ctx->d_trRhs, batch);
+                } else {
+                    femfct_enqueue_obs_load(ctx, ol, ctx->d_trRhs, batch);
+                }
                 rhs = make_ref(ctx->d_trRhs);
             } else if (g_traj) {   // coefficient at level n, adjoint at level n+1; all-time: the misfit load in the same launch
                 ReactLoadSpec rl;
@@ -450,6 +485,37 @@ int femfct_linear_adjoint_react_obs(femfct_ctx* ctx, const double* Aadj_ell, con
     const ObsArgs obs{theta, tau, window};
     return solidbody_adjoint_sweep(ctx, Aadj_ell, zc, 1, g_traj, u_traj, uhat_traj, p_traj, num_steps, dt, eps, 1.0, 0.0, 0.0,
                                    0, batch, &obs);
+}
+
+// The snapshot sweeps with state bounds lower <= u_n <= upper as a Moreau-Yosida penalty (BoundArgs, kernels_bounds.hip;
+// added after ABI version 5, backward compatible)
+int femfct_solidbody_adjoint_bounds(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                                    const double* u_traj, const double* uhat_traj, const double* theta, double tau,
+                                    const double* window, const double* lower, const double* upper, double gamma,
+                                    const double* sigma, const double* window_s, double* p_traj, int32_t num_steps,
+                                    double dt, double eps, double rot_scale, double bx, double by, int32_t batch) {
+    const ObsArgs obs{theta, tau, window};
+    const BoundArgs bnd{lower, upper, gamma, sigma, window_s};
+    return solidbody_adjoint_sweep(ctx, Arot_ell, c_traj, c_shared, nullptr, u_traj, uhat_traj, p_traj, num_steps, dt, eps,
+                                   rot_scale, bx, by, 0, batch, &obs, &bnd);
+}
+
+int femfct_linear_adjoint_react_bounds(femfct_ctx* ctx, const double* Aadj_ell, const double* g_traj, const double* u_traj,
+                                       const double* uhat_traj, const double* theta, double tau, const double* window,
+                                       const double* lower, const double* upper, double gamma, const double* sigma,
+                                       const double* window_s, double* p_traj, int32_t num_steps, double dt, double eps,
+                                       int32_t batch) {
+    FEMFCT_ENTER(ctx);
+    ARG_TRY(ctx, ctx && ctx->structured, "structured mesh not set (femfct_set_mesh_square)");
+    ARG_TRY(ctx, theta, "theta is null");
+    ARG_TRY(ctx, Aadj_ell && g_traj && u_traj && uhat_traj && p_traj && num_steps >= 1 && batch >= 1, "bad argument");
+    const double* zc = nullptr;
+    int rc = zero_control(ctx, num_steps, &zc);
+    if (rc != FEMFCT_OK) return rc;
+    const ObsArgs obs{theta, tau, window};
+    const BoundArgs bnd{lower, upper, gamma, sigma, window_s};
+    return solidbody_adjoint_sweep(ctx, Aadj_ell, zc, 1, g_traj, u_traj, uhat_traj, p_traj, num_steps, dt, eps, 1.0, 0.0, 0.0,
+                                   0, batch, &obs, &bnd);
 }
 
 // per-step solver diagnostics of the most recent trajectory sweep: info[step*batch + b]

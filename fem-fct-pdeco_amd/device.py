@@ -402,6 +402,41 @@ class Context:
                                                int(num_steps), int(batch), _host_ptr(out)))
         return out
 
+    # -- state bounds: P = gamma/2 sum_n sigma_n sum_i ml_i ws_i v_{n,i}^2, v = u - clip(u, lower, upper) ----------------
+    def solidbody_adjoint_bounds(self, Arot, c_traj, u_traj, uhat_traj, theta, tau, window, lower, upper, gamma, sigma,
+                                 window_s, p_traj, num_steps, dt, eps=0.0, rot_scale=1.0, drift=(1.0, 1.0), batch=1,
+                                 c_shared=False):
+        """:meth:`solidbody_adjoint_obs` with the penalty of the state bounds: p_Nt loses sigma[Nt] gamma ws .* v_Nt, the
+        load of level n loses (sigma[n]/dt) gamma ml .* ws .* v_n.  ``lower`` / ``upper`` / ``window_s``: n device doubles
+        or None (not both bounds); ``sigma``: num_steps + 1 device doubles."""
+        check(self.handle, lib.femfct_solidbody_adjoint_bounds(
+            self.handle, dptr(Arot), dptr(c_traj), int(bool(c_shared)), dptr(u_traj), dptr(uhat_traj), dptr(theta),
+            float(tau), dptr(window), dptr(lower), dptr(upper), float(gamma), dptr(sigma), dptr(window_s), dptr(p_traj),
+            int(num_steps), float(dt), float(eps), float(rot_scale), float(drift[0]), float(drift[1]), int(batch)))
+
+    def linear_adjoint_react_bounds(self, Aadj, g_traj, u_traj, uhat_traj, theta, tau, window, lower, upper, gamma, sigma,
+                                    window_s, p_traj, num_steps, dt, eps, batch=1):
+        """The same for the sweep with the explicit reaction term."""
+        check(self.handle, lib.femfct_linear_adjoint_react_bounds(
+            self.handle, dptr(Aadj), dptr(g_traj), dptr(u_traj), dptr(uhat_traj), dptr(theta), float(tau), dptr(window),
+            dptr(lower), dptr(upper), float(gamma), dptr(sigma), dptr(window_s), dptr(p_traj), int(num_steps), float(dt),
+            float(eps), int(batch)))
+
+    def bound_load(self, uhat, u, theta, sigma, level, dt, lower, upper, gamma, out, window=None, g=None, x=None,
+                   window_s=None, batch=1):
+        """out = (theta[level]/dt) Mw (uhat - u) [- Mg(g) x] - (sigma[level]/dt) gamma ml .* ws .* v(u) for one level."""
+        check(self.handle, lib.femfct_bound_load(self.handle, dptr(uhat), dptr(u), dptr(theta), dptr(sigma), int(level),
+                                                 float(dt), dptr(window), dptr(g), dptr(x), dptr(lower), dptr(upper),
+                                                 float(gamma), dptr(window_s), dptr(out), int(batch)))
+
+    def bound_cost(self, u_traj, sigma, lower, upper, gamma, num_steps, window_s=None, batch=1) -> np.ndarray:
+        """``(batch, 3)``: the penalty P, the largest |v| and the number of v != 0 over the penalised (level, node) pairs
+        per batch member (``sigma``: device doubles)."""
+        out = np.empty((batch, 3))
+        check(self.handle, lib.femfct_bound_cost(self.handle, dptr(u_traj), dptr(sigma), dptr(lower), dptr(upper),
+                                                 float(gamma), dptr(window_s), int(num_steps), int(batch), _host_ptr(out)))
+        return out
+
     def assemble_weighted_mass(self, f, out: DeviceArray | None = None) -> DeviceArray:
         """``assemble_sparse(f_h*u*v*dx)`` for the P1 function with the nodal values ``f`` (ELL)."""
         if out is None:

@@ -118,6 +118,113 @@ class Observations:
         return self
 
 
+class StateBounds:
+    """Bounds lower <= u_n <= upper on the state as a Moreau-Yosida penalty (an extension: the reference has none),
+
+        v_n = u_n - clip(u_n, lower, upper)              the nodal violation, signed
+        P(u) = gamma/2 sum_n sigma_n sum_i ml_i omega_i v_{n,i}^2,      J_gamma = J + P
+
+    with the lumped mass ml (the max acts node by node; the choice of the sparse controls' ||c||_{1,h}).  ``lower`` /
+    ``upper``: a scalar or n nodal values in the problem's DoF order, +-inf allowed, None: no bound on that side;
+    ``gamma`` >= 0; ``levels``: strictly increasing time levels in 1..num_steps (default: all of them; level 0 is the
+    fixed initial condition); ``weights``: one sigma_n >= 0 per level (default: the problem's dt); ``window``: nodal
+    omega >= 0 (None: 1).  Derived for a problem with time step dt, as the sweep and the cost take them:
+
+        sigma(dt)   num_steps + 1 level weights, sigma[0] = 0: the step to level n < num_steps is loaded with
+                    -(sigma[n]/dt) gamma ml .* omega .* v_n on top of the tracking load
+        tau_s(dt)   sigma[num_steps]: p_Nt gets -tau_s gamma omega .* v_Nt, nodal as the tracking terminal condition
+        cost_w(dt)  the weights of P, = sigma
+
+    :meth:`with_gamma` gives the same bounds with another gamma (continuation)."""
+
+    def __init__(self, num_steps, lower=None, upper=None, gamma=1.0, levels=None, weights=None, window=None):
+        Nt = int(num_steps)
+        if Nt < 1:
+            raise ValueError(f"num_steps = {num_steps}: must be >= 1")
+        if lower is None and upper is None:
+            raise ValueError("no bound: lower and upper are both None")
+        lo = None if lower is None else np.array(lower, dtype=np.float64).ravel()
+        hi = None if upper is None else np.array(upper, dtype=np.float64).ravel()
+        for name, b in (("lower", lo), ("upper", hi)):
+            if b is not None and (b.size == 0 or np.isnan(b).any()):
+                raise ValueError(f"{name} is empty or holds NaN")
+        if lo is not None and hi is not None:
+            if lo.size != hi.size and 1 not in (lo.size, hi.size):
+                raise ValueError(f"lower of {lo.size} values, upper of {hi.size}")
+            if np.any(lo > hi):
+                raise ValueError("lower > upper")
+        lv = np.arange(1, Nt + 1) if levels is None else np.asarray(levels)
+        if lv.ndim != 1 or lv.size == 0:
+            raise ValueError("no penalised levels")
+        if not np.all(lv == np.floor(lv)):
+            raise ValueError("levels must be integers")
+        lv = lv.astype(np.int64)
+        if lv.min() < 1 or lv.max() > Nt:
+            raise ValueError(f"levels must lie in 1..num_steps = {Nt}")
+        if np.any(np.diff(lv) <= 0):
+            raise ValueError("levels must be strictly increasing (sorted, no duplicates)")
+        w = np.ones(lv.size) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
+        if w.size != lv.size:
+            raise ValueError(f"{w.size} weights for {lv.size} levels")
+        if not np.all(w >= 0):
+            raise ValueError("weights must be >= 0")
+        if window is not None:
+            window = np.array(window, dtype=np.float64).ravel()
+            if not np.all(window >= 0):
+                raise ValueError("window must be >= 0 everywhere")
+        level_w = np.zeros(Nt + 1)
+        level_w[lv] = w
+        self.num_steps, self.levels, self.lower, self.upper, self.window = Nt, lv, lo, hi, window
+        self._level_w, self._per_dt = level_w, weights is None
+        for a in (lv, lo, hi, window, level_w):
+            if a is not None:
+                a.setflags(write=False)
+        self._fields = object()         # what the device copies hang on: shared by the with_gamma() variants
+        self._set_gamma(gamma)
+
+    def _set_gamma(self, gamma):
+        g = float(gamma)
+        if not (g >= 0 and np.isfinite(g)):
+            raise ValueError(f"gamma = {gamma}: must be finite and >= 0")
+        self.gamma = g
+
+    def with_gamma(self, gamma):
+        """The same bounds, levels, weights and window with another penalty weight."""
+        other = StateBounds.__new__(StateBounds)
+        other.__dict__.update(self.__dict__)
+        other._set_gamma(gamma)
+        return other
+
+    def sigma(self, dt):
+        return self._level_w * float(dt) if self._per_dt else self._level_w
+
+    def tau_s(self, dt):
+        return float(self.sigma(dt)[self.num_steps])
+
+    def cost_w(self, dt):
+        return self.sigma(dt)
+
+    def nodal(self, nodes):
+        """``(lower, upper, window)`` as ``nodes`` values each (scalars spread out), None where absent."""
+        spread = lambda b: None if b is None else (np.full(int(nodes), b[0]) if b.size == 1 else b)
+        return spread(self.lower), spread(self.upper), self.window
+
+    def pairs(self, nodes, dt):
+        """the number of penalised (level, node) pairs: sigma_n != 0 and omega_i != 0"""
+        return int(np.count_nonzero(self.sigma(dt))) * (int(nodes) if self.window is None else int(np.count_nonzero(self.window)))
+
+    def check(self, num_steps, nodes):
+        """Raises ValueError unless these bounds fit a problem of ``num_steps`` steps and ``nodes`` DoFs."""
+        if self.num_steps != int(num_steps):
+            raise ValueError(f"state bounds of {self.num_steps} steps for a problem of {num_steps}")
+        for name, b in (("lower", self.lower), ("upper", self.upper)):
+            if b is not None and b.size not in (1, int(nodes)):
+                raise ValueError(f"{name} of {b.size} values, expected 1 or {nodes}")
+        if self.window is not None and self.window.size != int(nodes):
+            raise ValueError(f"window of {self.window.size} values, expected {nodes}")
+        return self
+
+
 def _need_obs(optim, obs):
     if optim not in OPTIMS:
         raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of {list(OPTIMS)}.")
@@ -266,8 +373,62 @@ class SolidBodyDrift:
             cache[id(obs)] = hit
         return hit[1:]
 
-    def adjoint(self, c, u, uhat, p, optim="finaltime", batch=None, c_shared=False, obs=None):
-        """optim="snapshots": ``uhat`` is a trajectory read at the levels ``obs`` observes only."""
+    def bounds_device(self, bounds: StateBounds):
+        """``(sigma, lower, upper, window)`` of ``bounds`` on the device (uploaded once per set of bounds: the
+        :meth:`StateBounds.with_gamma` variants share them)."""
+        cache = self.__dict__.setdefault("_bounds_cache", {})
+        hit = cache.get(id(bounds._fields))
+        if hit is None or hit[0] is not bounds._fields:
+            bounds.check(self.num_steps, self.n)
+            lo, hi, win = bounds.nodal(self.n)
+            up = lambda a: None if a is None else self.ctx.array(np.ascontiguousarray(a))
+            hit = (bounds._fields, self.ctx.array(np.ascontiguousarray(bounds.sigma(self.dt))), up(lo), up(hi), up(win))
+            cache[id(bounds._fields)] = hit
+        return hit[1:]
+
+    def _corner(self, optim, obs, uhat, batch):
+        """The observations and the target trajectory of a mode, for the sweeps with state bounds (which are snapshot
+        sweeps): final-time and all-time are their :class:`Observations` corners, the final-time target copied to level
+        num_steps of a trajectory-sized buffer that is kept."""
+        if _need_obs(optim, obs):
+            return obs, uhat
+        corners = self.__dict__.setdefault("_corner_obs", {})
+        if optim not in corners:
+            corners[optim] = (Observations.finaltime(self.num_steps) if optim == "finaltime"
+                              else Observations.alltime(self.num_steps, self.dt))
+        if optim == "alltime":
+            return corners[optim], uhat
+        buf = self.__dict__.get("_corner_target")
+        if buf is None or buf.count < batch * self.tlen:
+            if buf is not None:
+                buf.free()
+            buf = self.__dict__["_corner_target"] = self.ctx.zeros(batch * self.tlen)
+        for b in range(batch):
+            buf.copy_from(uhat, self.n, dst_off=b * self.tlen + self.num_steps * self.n, src_off=b * self.n)
+        return corners[optim], buf
+
+    def bound_stats(self, u, bounds: StateBounds, batch=None):
+        """``(penalty, max_violation, violated_fraction)`` of the trajectories ``u``, one value per batch member each: P,
+        the largest |v| and the share of v != 0 among the penalised (level, node) pairs, from one fused pass."""
+        B = self.batch if batch is None else batch
+        sigma, lo, hi, win = self.bounds_device(bounds)
+        out = self.ctx.bound_cost(u, sigma, lo, hi, bounds.gamma, self.num_steps, win, batch=B)
+        out[:, 2] /= max(1, bounds.pairs(self.n, self.dt))
+        self.last_bound_stats = out
+        return out[:, 0], out[:, 1], out[:, 2]
+
+    def adjoint(self, c, u, uhat, p, optim="finaltime", batch=None, c_shared=False, obs=None, state_bounds=None):
+        """optim="snapshots": ``uhat`` is a trajectory read at the levels ``obs`` observes only.  ``state_bounds`` (a
+        :class:`StateBounds`): the adjoint of J + P, the penalty load in the load launch of every step."""
+        if state_bounds is not None:
+            B = self.batch if batch is None else batch
+            obs, uhat = self._corner(optim, obs, uhat, B)
+            theta, _, window = self.obs_device(obs)
+            sigma, lo, hi, win = self.bounds_device(state_bounds)
+            self.ctx.solidbody_adjoint_bounds(self.Arot, c, u, uhat, theta, obs.tau, window, lo, hi, state_bounds.gamma,
+                                              sigma, win, p, self.num_steps, self.dt, self.eps, self.rot_scale, self.drift,
+                                              B, c_shared)
+            return
         if _need_obs(optim, obs):
             theta, _, window = self.obs_device(obs)
             self.ctx.solidbody_adjoint_obs(self.Arot, c, u, uhat, theta, obs.tau, window, p, self.num_steps, self.dt,
@@ -312,7 +473,10 @@ class SolidBodyDrift:
             buf = self.__dict__["_ivl_buf"] = self.ctx.empty(count)
         return buf.ptr, buf.ptr + 8 * (count // 2)
 
-    def cost(self, u, target, c, beta, optim, batch=None, obs=None):
+    def cost(self, u, target, c, beta, optim, batch=None, obs=None, state_bounds=None):
+        """J per batch member.  ``state_bounds``: J + P, the statistics of the pass kept in ``last_bound_stats``."""
+        if state_bounds is not None:
+            return self.cost(u, target, c, beta, optim, batch=batch, obs=obs) + self.bound_stats(u, state_bounds, batch)[0]
         if _need_obs(optim, obs):       # every member (all Armijo trials of a batched sweep) in one call
             B = self.batch if batch is None else batch
             _, cost_w, window = self.obs_device(obs)
@@ -334,14 +498,14 @@ class SolidBodyDrift:
             u.free()
         return uk
 
-    def solve_adjoint(self, ck, uk, uhat, pk, optim="finaltime", obs=None):
+    def solve_adjoint(self, ck, uk, uhat, pk, optim="finaltime", obs=None, state_bounds=None):
         """finaltime.py:200-221 / alltime.py:232-259: fills and returns ``pk``."""
         c = self.ctx.array(ck)
         u = self.ctx.array(uk)
         uh = self.ctx.array(uhat)
         p = self.ctx.zeros(self.tlen)
         try:
-            self.adjoint(c, u, uh, p, optim, batch=1, obs=obs)
+            self.adjoint(c, u, uh, p, optim, batch=1, obs=obs, state_bounds=state_bounds)
             p.download(pk)
         finally:
             for a in (c, u, uh, p):
@@ -380,9 +544,9 @@ class LinearSourceControl(SolidBodyDrift):
         """advection_FCT_PDECO_alltime_exact.py:236-253 (src = g + c, both trajectories)"""
         self.forward(self._zero_c, u, batch=batch, c_shared=True, src=src)
 
-    def adjoint_state(self, u, uhat, p, optim="alltime", batch=None, obs=None):
+    def adjoint_state(self, u, uhat, p, optim="alltime", batch=None, obs=None, state_bounds=None):
         """:259-274 (all-time) / advection_FCT_PDECO_finaltime.py (final-time)"""
-        self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True, obs=obs)
+        self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True, obs=obs, state_bounds=state_bounds)
 
     def descent_direction(self, c, p, beta, d, control_time=None):
         """advection_FCT_PDECO_alltime_exact.py:278: d = -(beta*c - p), every level, the script's operation order.
@@ -407,10 +571,10 @@ class LinearSourceControl(SolidBodyDrift):
             u.free()
         return uk
 
-    def solve_adjoint_state(self, uk, uhat, pk, optim="alltime", obs=None):
+    def solve_adjoint_state(self, uk, uhat, pk, optim="alltime", obs=None, state_bounds=None):
         u, uh, p = self.ctx.array(uk), self.ctx.array(uhat), self.ctx.zeros(self.tlen)
         try:
-            self.adjoint_state(u, uh, p, optim, batch=1, obs=obs)
+            self.adjoint_state(u, uh, p, optim, batch=1, obs=obs, state_bounds=state_bounds)
             p.download(pk)
         finally:
             for a in (u, uh, p):
@@ -459,7 +623,15 @@ class LinearReactionSourceControl(LinearSourceControl):
         self.ctx.linear_forward_react(self.Arot, src, self._react, u, self.num_steps, self.dt, self.eps,
                                       self.batch if batch is None else batch)
 
-    def adjoint_state(self, u, uhat, p, optim="finaltime", batch=None, obs=None):
+    def adjoint_state(self, u, uhat, p, optim="finaltime", batch=None, obs=None, state_bounds=None):
+        if state_bounds is not None:
+            B = self.batch if batch is None else batch
+            obs, uhat = self._corner(optim, obs, uhat, B)
+            theta, _, window = self.obs_device(obs)
+            sigma, lo, hi, win = self.bounds_device(state_bounds)
+            self.ctx.linear_adjoint_react_bounds(self.Aadj, self._react, u, uhat, theta, obs.tau, window, lo, hi,
+                                                 state_bounds.gamma, sigma, win, p, self.num_steps, self.dt, self.eps, B)
+            return
         if _need_obs(optim, obs):
             theta, _, window = self.obs_device(obs)
             self.ctx.linear_adjoint_react_obs(self.Aadj, self._react, u, uhat, theta, obs.tau, window, p, self.num_steps,
@@ -503,32 +675,53 @@ def finaltime_exact_fields(t, X, Y, T=0.1, beta=0.1, c_lower=0.0, c_upper=1.0, e
     return dict(u=u, p=p, c=c, g=g, f=f, uhat=u.copy(), div=div)
 
 
+def _bounds_kw(prob, state_bounds):
+    """the keyword the loops pass on to ``prob.adjoint`` / ``prob.cost`` (none without state bounds: today's calls)"""
+    if state_bounds is None:
+        return {}
+    if not isinstance(state_bounds, StateBounds):
+        raise ValueError("state_bounds must be a StateBounds")
+    state_bounds.check(prob.num_steps, prob.n)
+    return dict(state_bounds=state_bounds)
+
+
+def _record_bounds(prob, hist, member):
+    """the statistics of batch member ``member`` of the last cost pass, the accepted iterate's, into the history"""
+    P, vmax, frac = prob.last_bound_stats[member]
+    hist.setdefault("penalty", []).append(float(P))
+    hist.setdefault("max_violation", []).append(float(vmax))
+    hist.setdefault("violated_fraction", []).append(float(frac))
+
+
 def pgd_solidbody_finaltime(prob: SolidBodyDrift, u0, uhat_T, c0, beta, c_lower, c_upper, iters,
-                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None):
+                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
+                            state_bounds=None):
     """Final-time variant of :func:`pgd_solidbody` (advection_solidbody_FCT_PDECO_finaltime_Garvie.py)."""
     return pgd_solidbody(prob, u0, uhat_T, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="finaltime", control_time=control_time)
+                         optim="finaltime", control_time=control_time, state_bounds=state_bounds)
 
 
 def pgd_solidbody_alltime(prob: SolidBodyDrift, u0, uhat_all, c0, beta, c_lower, c_upper, iters,
-                          gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None):
+                          gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
+                          state_bounds=None):
     """All-time variant (advection_solidbody_FCT_PDECO_alltime_Garvie.py, config C5's loop): ``uhat_all``
     is the target trajectory ((Nt+1)*n, level 0 = u0)."""
     return pgd_solidbody(prob, u0, uhat_all, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="alltime", control_time=control_time)
+                         optim="alltime", control_time=control_time, state_bounds=state_bounds)
 
 
 def pgd_solidbody_snapshots(prob: SolidBodyDrift, u0, uhat, obs: Observations, c0, beta, c_lower, c_upper, iters,
-                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None):
+                            gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
+                            state_bounds=None):
     """Snapshot variant of :func:`pgd_solidbody`: ``uhat`` is a (num_steps+1)*n trajectory of which only the levels that
     ``obs`` observes are read (the others may hold anything, NaN included)."""
     return pgd_solidbody(prob, u0, uhat, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="snapshots", obs=obs, control_time=control_time)
+                         optim="snapshots", obs=obs, control_time=control_time, state_bounds=state_bounds)
 
 
 def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters,
                   gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None,
-                  control_time=None):
+                  control_time=None, state_bounds=None):
     """Projected gradient descent for the drift-control problem, following the loop of
     advection_solidbody_FCT_PDECO_finaltime_Garvie.py:164-330 / ..._alltime_Garvie.py:164-340 step for step:
 
@@ -547,8 +740,11 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     :class:`Observations`; u is seeded with the target at the observed levels (both modes above, seen as observations).
     ``control_time`` (a :class:`ControlIntervals`): the control is constant in time on its intervals; d is projected onto
     these controls and ``c0`` must be one of them (ValueError otherwise).  None: the free space-time control.
+    ``state_bounds`` (a :class:`StateBounds`): the loop descends J + P, and the history gains ``penalty``,
+    ``max_violation`` and ``violated_fraction`` of the accepted iterate, from the pass that costs the trials.
     Returns ``(u, p, c, history)`` as NumPy arrays + a dict of per-iteration scalars."""
     snap = _need_obs(optim, obs)
+    sbk = _bounds_kw(prob, state_bounds)
     alltime = optim == "alltime" or snap         # (the target is a trajectory)
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     if control_time is not None:
@@ -582,14 +778,14 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
         u.copy_from(uh, n, dst_off=Nt * n)                 # uk[num_steps*nodes:] = uhat_T
     try:
         for it in range(iters):
-            prob.adjoint(c_prev, u, uh, p, optim, batch=1, obs=obs)
+            prob.adjoint(c_prev, u, uh, p, optim, batch=1, obs=obs, **sbk)
             if control_time is None:
                 prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs)
             else:
                 prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, control_time=control_time)
             ctx.project_control(c_prev, s0, d, c_lower, c_upper, c, tl)
             prob.forward(c, u, batch=1)
-            J_k = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs)[0])
+            J_k = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs, **sbk)[0])
             svals = [s0 * (1 / 2 ** k) for k in range(max_armijo)]
             accepted = None
             if speculative:
@@ -597,7 +793,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
                     ctx.project_control(c, s, d, c_lower, c_upper, cB.ptr + 8 * k * tl, tl)
                     ckB.copy_from(c, tl, dst_off=k * tl)
                 prob.forward(cB, uB, batch=B)
-                J = prob.cost(uB, uhB, cB, beta, optim, batch=B, obs=obs)
+                J = prob.cost(uB, uhB, cB, beta, optim, batch=B, obs=obs, **sbk)
                 stat = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=B)
                 margins = []
                 for k, s in enumerate(svals):
@@ -614,13 +810,15 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
                     accepted = k
                     ctx.project_control(c, s, d, c_lower, c_upper, cB, tl)
                     prob.forward(cB, uB, batch=1)
-                    J_acc = float(prob.cost(uB, uh, cB, beta, optim, batch=1, obs=obs)[0])
+                    J_acc = float(prob.cost(uB, uh, cB, beta, optim, batch=1, obs=obs, **sbk)[0])
                     stat = float(ctx.l2_norm_sq_Q(cB, c, Nt, dt)[0])
                     margins.append((J_acc - J_k + gam / s * stat) / abs(J_k))
                     if not (J_acc - J_k > -gam / s * stat):
                         break
                 c_prev.copy_from(cB, tl)
                 u.copy_from(uB, tl)
+            if sbk:
+                _record_bounds(prob, hist, accepted if speculative else 0)
             hist["cost"].append(J_acc)
             hist["wall"].append(time.perf_counter())          # (J_acc is a read-back: the iteration's device work is done)
             hist["armijo_margin"].append(margins)
@@ -806,7 +1004,7 @@ def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c
 
 def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
                        increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
-                       control_time=None):
+                       control_time=None, state_bounds=None):
     """Projected gradient descent for the linear source-control problem, the loop of
     advection_FCT_PDECO_alltime_exact.py:212-330 (optim="alltime", stop="both") and advection_FCT_PDECO_finaltime.py:
     170-280 (optim="finaltime", stop="cost"):
@@ -831,10 +1029,16 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
     last iteration's state and adjoint (at the control that iteration started from), c the last accepted control.
     hist["cost"][k] is the accepted J_acc (the linear estimate in linear mode); hist["cost_state"][k] the cost
     J(S(g + c_k), c_k) of the re-solved state at the control iteration k started from, so hist["cost_state"][k + 1]
-    re-solves hist["cost"][k]."""
+    re-solves hist["cost"][k].
+    ``state_bounds`` (a :class:`StateBounds`; increment="resolve" only): the loop descends J + P, and the history gains
+    ``penalty``, ``max_violation`` and ``violated_fraction`` of the accepted iterate."""
     snap = _need_obs(optim, obs)
     if increment not in ("linear", "resolve"):
         raise ValueError(f"Invalid value for 'increment': '{increment}'. Must be one of ['linear', 'resolve'].")
+    if state_bounds is not None and increment == "linear":
+        raise ValueError("state_bounds needs increment='resolve': the fused linear-increment trial costs know the "
+                         "all-time and final-time modes only")
+    sbk = _bounds_kw(prob, state_bounds)
     if snap and increment == "linear":
         raise ValueError("optim='snapshots' needs increment='resolve': the fused linear-increment trial costs know the "
                          "all-time and final-time modes only")
@@ -879,7 +1083,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             for k in range(K):
                 uB.copy_from(u, n, dst_off=k * tl)              # level 0 of every trial state = u0
                 uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
-        cost = lambda uu, cc: float(prob.cost(uu, uh, cc, beta, optim, batch=1, obs=obs)[0])
+        cost = lambda uu, cc: float(prob.cost(uu, uh, cc, beta, optim, batch=1, obs=obs, **sbk)[0])
         J_ref = 10 * cost(u, c)                                 # alltime_exact.py:212 / finaltime.py:170
         hist = dict(cost=[], cost_state=[], armijo_k=[], step=[], stop_crit=[], stop_crit2=[], armijo_margin=[],
                     wall=[], wall0=time.perf_counter())
@@ -890,7 +1094,10 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
                 ctx.axpby(tl, 1.0, gd, 1.0, c, src)
             prob.state(src, u, batch=1)
             hist["cost_state"].append(cost(u, c))
-            prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs) if snap else prob.adjoint_state(u, uh, p, optim, batch=1)
+            if snap or sbk:
+                prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs, **sbk)
+            else:
+                prob.adjoint_state(u, uh, p, optim, batch=1)
             if control_time is None:
                 prob.descent_direction(c, p, beta, d)
             else:
@@ -901,7 +1108,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             else:
                 ctx.source_trials(c, d, s0, K, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
                 prob.state(srcB, uB, batch=K)
-                J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs)
+                J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs, **sbk)
                 for k in range(K):
                     ckB.copy_from(c, tl, dst_off=k * tl)
                 dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=K)
@@ -912,6 +1119,8 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
                 if J[k] - J_ref <= -gam / s * dist[k]:
                     break
             J_acc, dist_acc = float(J[acc]), float(dist[acc])
+            if sbk:
+                _record_bounds(prob, hist, acc)
             nc = float(ctx.l2_norm_sq_Q(c, None, Nt, dt)[0])
             stop1 = dist_acc / nc if nc > 0 else np.inf
             stop2 = abs(J_ref - J_acc) / abs(J_ref)
@@ -1114,7 +1323,8 @@ def _first_accepted(J, dist, J_k, svals, gam, margins):
 
 
 def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters, memory=5, gam=1e-4, s0=1.0,
-                    max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None, control_time=None):
+                    max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None, control_time=None,
+                    state_bounds=None):
     """Projected L-BFGS descent for the drift-control problem: the sweeps, cost, direction kernels and Armijo test of
     :func:`pgd_solidbody` with the direction of a :class:`LimitedMemory` of ``memory`` pairs.  Per iteration, at the
     control c with u = S(c) and J = J(u, c):
@@ -1128,12 +1338,13 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
     loop, not a restatement of a script), so an accepted cost never exceeds the previous one.  ``memory=0`` is plain
     projected gradient with this search.  ``speculative=True`` evaluates the ``max_armijo`` trials as one batch, as
     pgd_solidbody does.  With ``control_time`` s, y, g and the free set are constant on every interval, so the iterates
-    stay piecewise constant bit for bit.  ``optim``, ``obs``, ``tol``: as in pgd_solidbody.
+    stay piecewise constant bit for bit.  ``optim``, ``obs``, ``tol``, ``state_bounds``: as in pgd_solidbody.
 
     Returns ``(u, p, c, history)``; history: ``cost``, ``armijo_k``, ``armijo_margin`` (every trial looked at, the
     quasi-Newton ones first), ``used`` ("qn" / "g"), ``pairs``, ``free_fraction``, ``sweeps`` (state and adjoint sweeps so
     far, counting the trials a sequential search looks at), ``step``, ``rel_change``, ``wall``, ``cost0``, ``stalled``."""
     snap = _need_obs(optim, obs)
+    sbk = _bounds_kw(prob, state_bounds)
     alltime = optim == "alltime" or snap
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     K = int(max_armijo)
@@ -1171,12 +1382,13 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
         for k in range(B):
             uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
             uB.copy_from(u0d, n, dst_off=k * tl)          # level 0 of every trial trajectory = the initial condition
-        cost = lambda uu, hh, cc, b: prob.cost(uu, hh, cc, beta, optim, batch=b, obs=obs)
+        cost = lambda uu, hh, cc, b: prob.cost(uu, hh, cc, beta, optim, batch=b, obs=obs, **sbk)
         prob.forward(c, u, batch=1)
         J0 = float(cost(u, uh, c, 1)[0])
+        bstat = {}
 
         def gradient():
-            prob.adjoint(c, u, uh, p, optim, batch=1, obs=obs)
+            prob.adjoint(c, u, uh, p, optim, batch=1, obs=obs, **sbk)
             if control_time is None:
                 prob.descent_direction(c, u, p, beta, d, scratch=rhs)
             else:
@@ -1207,10 +1419,13 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
             off = t * tl if speculative else 0
             c.copy_from(cB, tl, src_off=off)
             u.copy_from(uB, tl, src_off=off)
+            if sbk:         # (the last cost pass is that of the search that found t)
+                _record_bounds(prob, bstat, t if speculative else 0)
 
         stop = lambda J, Jt, dist: tol is not None and abs(J - Jt) / abs(J) < tol
         hist = _lbfgs_iterate(ctx, lm, tl, c, g, qn_bufs, J0, gradient, search, take, c_lower, c_upper, int(iters), gam,
                               s0, K, stop)
+        hist.update(bstat)
         return u.download(), p.download(), c.download(), hist
     finally:
         lm.close()
@@ -1220,7 +1435,7 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
 
 def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
                          memory=5, gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
-                         control_time=None):
+                         control_time=None, state_bounds=None):
     """Projected L-BFGS descent for the linear source-control problem (:class:`LinearSourceControl`,
     :class:`LinearReactionSourceControl`): the iteration of :func:`lbfgs_solidbody` with the gradient
     -descent_direction = beta c - p, the trial controls and sources of ``femfct_source_trials`` and the ``max_armijo``
@@ -1230,6 +1445,7 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
     stop_crit = ||c_{k+1} - c_k||^2_Q / ||c_k||^2_Q >= tol, and fewer than ``max_iters`` iterations have run.
     Arguments and return value as pgd_source_control; the history is lbfgs_solidbody's with ``stop_crit``, ``stop_crit2``."""
     snap = _need_obs(optim, obs)
+    sbk = _bounds_kw(prob, state_bounds)
     if stop not in ("both", "cost"):
         raise ValueError(f"Invalid value for 'stop': '{stop}'. Must be one of ['both', 'cost'].")
     K = int(max_armijo)
@@ -1273,11 +1489,14 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
         if gd is not None:
             ctx.axpby(tl, 1.0, gd, 1.0, c, src)
         prob.state(src, u, batch=1)
-        J0 = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs)[0])
+        J0 = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs, **sbk)[0])
         crit = dict(stop_crit=[], stop_crit2=[])
 
         def gradient():
-            prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs) if snap else prob.adjoint_state(u, uh, p, optim, batch=1)
+            if snap or sbk:
+                prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs, **sbk)
+            else:
+                prob.adjoint_state(u, uh, p, optim, batch=1)
             if control_time is None:
                 prob.descent_direction(c, p, beta, d)
             else:
@@ -1287,7 +1506,7 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
         def search(dirv, J_k, svals, margins):
             ctx.source_trials(c, dirv, s0, K, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
             prob.state(srcB, uB, batch=K)
-            J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs)
+            J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs, **sbk)
             for k in range(K):
                 ckB.copy_from(c, tl, dst_off=k * tl)
             dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=K)
@@ -1297,6 +1516,8 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
         def take(t):
             c.copy_from(cB, tl, src_off=t * tl)
             u.copy_from(uB, tl, src_off=t * tl)
+            if sbk:
+                _record_bounds(prob, crit, t)
 
         def stop_test(J, Jt, dist):
             nc = float(ctx.l2_norm_sq_Q(qn_bufs[1], None, Nt, dt)[0])      # (c_old: the control the step started from)

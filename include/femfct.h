@@ -289,6 +289,40 @@ int femfct_obs_load(femfct_ctx* ctx, const double* a_dev, const double* b_dev, c
  * result of a member does not depend on the batch size.  Synchronises. */
 int femfct_obs_cost(femfct_ctx* ctx, const double* u_traj, const double* uhat_traj, const double* cost_w_dev,
                     const double* window_dev, int32_t num_steps, int32_t batch, double* out_host);
+/* State bounds lower <= u_n <= upper as a Moreau-Yosida penalty on top of the snapshot tracking (added after ABI version 5,
+ * backward compatible; an extension without a counterpart in the reference):
+ *   v_n = u_n - clip(u_n, lower, upper),   P = gamma/2 sum_n sigma[n] sum_i ml_i window_s_i v_{n,i}^2,   J_gamma = J + P
+ * with the lumped mass ml of the context's mesh.  The adjoint sweep ends in
+ * p_Nt = tau * omega .* (uhat_Nt - u_Nt) - sigma[num_steps] gamma window_s .* v_Nt and loads the step to level n with
+ * (theta[n]/dt) Mw (uhat_n - u_n) - (sigma[n]/dt) gamma ml .* window_s .* v_n in the one load launch of the step.
+ * lower, upper: n doubles on the device in the problem's DoF order (+-inf allowed), either may be NULL (no bound on that
+ * side), not both.  sigma: num_steps + 1 level weights >= 0 ON THE DEVICE (sigma[0] = 0 for a fixed initial condition; a
+ * level of zero weight is not read for the penalty, the last level included, and no level is with gamma = 0).  window_s: n doubles >= 0 on the device, or NULL (1).  gamma: finite,
+ * >= 0.  Without a violation the results are those of the _obs entry points, bit for bit.  A NaN in a penalised u_n gives
+ * a NaN load (the sweep fails as it does for a NaN state). */
+int femfct_solidbody_adjoint_bounds(femfct_ctx* ctx, const double* Arot_ell, const double* c_traj, int32_t c_shared,
+                                    const double* u_traj, const double* uhat_traj, const double* theta, double tau,
+                                    const double* window, const double* lower, const double* upper, double gamma,
+                                    const double* sigma, const double* window_s, double* p_traj, int32_t num_steps,
+                                    double dt, double eps, double rot_scale, double bx, double by, int32_t batch);
+int femfct_linear_adjoint_react_bounds(femfct_ctx* ctx, const double* Aadj_ell, const double* g_traj, const double* u_traj,
+                                       const double* uhat_traj, const double* theta, double tau, const double* window,
+                                       const double* lower, const double* upper, double gamma, const double* sigma,
+                                       const double* window_s, double* p_traj, int32_t num_steps, double dt, double eps,
+                                       int32_t batch);
+/* the load of one level on its own: out = (theta_dev[level]/dt) Mw (uhat - u) [- Mg(g) x]
+ * - (sigma_dev[level]/dt) gamma ml .* window_s .* v(u); uhat, u, x, out: n doubles per batch member, g (with x; both
+ * NULL: no reaction part) shared by the batch.  theta_dev[level] == 0: uhat is not read. */
+int femfct_bound_load(femfct_ctx* ctx, const double* uhat_dev, const double* u_dev, const double* theta_dev,
+                      const double* sigma_dev, int32_t level, double dt, const double* window_dev, const double* g_dev,
+                      const double* x_dev, const double* lower_dev, const double* upper_dev, double gamma,
+                      const double* window_s_dev, double* out_dev, int32_t batch);
+/* out_host[3 b + {0, 1, 2}] = P, the largest |v| and the number of v != 0 (as a double) of batch member b over the
+ * penalised (level, node) pairs, those with sigma_dev[n] != 0 and window_s_i != 0 (trajectories of (num_steps + 1)*n
+ * doubles).  The result of a member does not depend on the batch size.  Synchronises. */
+int femfct_bound_cost(femfct_ctx* ctx, const double* u_traj, const double* sigma_dev, const double* lower_dev,
+                      const double* upper_dev, double gamma, const double* window_s_dev, int32_t num_steps, int32_t batch,
+                      double* out_host);
 /* out_ell = assemble(f_h*u*v*dx) for the P1 function with nodal values f_dev (n doubles).  Synchronises. */
 int femfct_assemble_weighted_mass(femfct_ctx* ctx, const double* f_dev, double* out_ell);
 /* solver diagnostics of the most recent sweep: info_host[step*batch + b] */
