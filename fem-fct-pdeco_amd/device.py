@@ -610,6 +610,28 @@ class Context:
                                                          float(dt), _host_ptr(l1), _host_ptr(dist), _host_ptr(nnz)))
         return l1, dist, nnz
 
+    # -- ensemble drift control (solvers.ensemble_solidbody): one control, S weighted scenarios ------------------
+    def ensemble_drift_gradient_rhs(self, c, u, p, weights, beta, out, levels, drift=(1.0, 1.0)):
+        """out = -(beta M c + sum_s weights[s] * assemble(p_s (b.grad u_s) v dx)) for every level, one launch; ``u``, ``p``:
+        S trajectories of ``levels * n`` doubles, ``c``, ``out``: one; the sum in index order over the non-zero weights (a
+        scenario of weight 0 is not read).  S = 1 with weight 1 is ``drift_gradient_rhs`` bit for bit."""
+        w = _as_f64(weights).reshape(-1)
+        check(self.handle, lib.femfct_ensemble_drift_gradient_rhs(
+            self.handle, dptr(c), dptr(u), dptr(p), _host_ptr(w), int(w.size), float(beta), float(drift[0]), float(drift[1]),
+            dptr(out), int(levels)))
+
+    def ensemble_costs(self, u, uhat, cost_w, c, weights, beta, num_steps, dt, window=None, cref=None):
+        """``(T, J, dist)``: T[s] = ``obs_cost`` of scenario s, J = sum_s weights[s] T[s] + (0.5 beta) ``l2_norm_sq_Q(c)``,
+        dist = ``l2_norm_sq_Q(c - cref)`` (None without ``cref``), each bit for bit those calls' values, with one
+        read-back; ``u``, ``uhat``: S trajectories, ``c``, ``cref``: one each."""
+        w = _as_f64(weights).reshape(-1)
+        T, J = np.empty(max(w.size, 1)), np.empty(1)
+        dist = None if cref is None else np.empty(1)
+        check(self.handle, lib.femfct_ensemble_costs(
+            self.handle, dptr(u), dptr(uhat), dptr(cost_w), dptr(window), dptr(c), dptr(cref), _host_ptr(w), int(w.size),
+            float(beta), int(num_steps), float(dt), _host_ptr(T), _host_ptr(J), None if dist is None else _host_ptr(dist)))
+        return T, float(J[0]), (None if dist is None else float(dist[0]))
+
     # -- non-FCT species / PDE systems ---------------------------------------------------
     def descent_pointwise(self, count, beta, c, x, out, y=None, scale=1.0, divisor=1.0):
         """out = -(beta*c - t), t = x*y/divisor (y given) or scale*x"""

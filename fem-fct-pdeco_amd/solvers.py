@@ -1741,3 +1741,161 @@ def prox_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, alpha, c_
     finally:
         for a in bufs:
             a.free()
+
+
+# ---------------------------------------------------------------------------------------------- ensemble drift control
+# An extension (no reference call): one control for many scenarios, the sample-average form of control under uncertain
+# data.  The scenarios are the batch of every sweep.
+class Ensemble:
+    """S scenarios of a drift-control problem that share one control: initial conditions ``u0`` (S, n), targets ``uhat``
+    (S, n) for final-time tracking, else (S, (num_steps + 1) * n), and ``weights`` pi_s >= 0 (default uniform), finite
+    with a positive sum, stored normalised to sum 1.  A scenario of weight 0 is carried along (its state, adjoint and
+    cost are computed) and does not enter the cost or the gradient."""
+
+    def __init__(self, u0, uhat, weights=None):
+        u0 = np.array(u0, dtype=np.float64)
+        uhat = np.array(uhat, dtype=np.float64)
+        if u0.ndim != 2 or u0.shape[0] < 1:
+            raise ValueError(f"u0 of shape {u0.shape}, expected (S, n)")
+        if uhat.ndim != 2 or uhat.shape[0] != u0.shape[0]:
+            raise ValueError(f"uhat of shape {uhat.shape} for {u0.shape[0]} scenarios, expected (S, n) or (S, tlen)")
+        S = u0.shape[0]
+        w = np.full(S, 1.0 / S) if weights is None else np.array(weights, dtype=np.float64).ravel()
+        if w.size != S:
+            raise ValueError(f"{w.size} weights for {S} scenarios")
+        if not (np.all(np.isfinite(w)) and np.all(w >= 0) and w.sum() > 0):
+            raise ValueError("weights must be finite and >= 0 with a positive sum")
+        if weights is not None:
+            w = w / w.sum()
+        self.u0, self.uhat, self.weights = u0, uhat, w
+        for a in (u0, uhat, w):
+            a.setflags(write=False)
+
+    @property
+    def S(self):
+        return self.u0.shape[0]
+
+
+def ensemble_solidbody(prob: SolidBodyDrift, scenarios: Ensemble, c0, beta, c_lower, c_upper, iters, memory=0, gam=1e-4,
+                       s0=1.0, max_armijo=10, tol=None, optim="finaltime", obs=None, control_time=None, state_bounds=None):
+    """Projected gradient (``memory=0``) or projected L-BFGS (``memory>0``) descent for one drift control that serves the
+    S ``scenarios`` (an :class:`Ensemble`),
+
+        J(c) = sum_s pi_s T_s(u_s(c)) + beta/2 ||c||^2_Q,      T_s = 1/2 sum_n cost_w[n] (u_{s,n} - uhat_{s,n})^T Mw (..)
+
+    with the tracking term of :class:`Observations` (``optim`` "finaltime" / "alltime" are its corners, "snapshots" takes
+    ``obs``).  It is the iteration of :func:`lbfgs_solidbody` (``_lbfgs_iterate``, :class:`LimitedMemory`) with three
+    callbacks of its own.  Every scenario has its own FCT state and FCT adjoint; the limiter is nonlinear, so the weights
+    are not folded into the adjoint loads and enter where the gradient is formed:
+
+        gradient   one adjoint sweep of S members with the shared control, rhs_l = -(beta M c_l + sum_s pi_s
+                   assemble(p_{s,l} (b.grad u_{s,l}) v dx)) in one launch, d = ChebSI(rhs) -- num_steps + 1 mass solves
+                   whatever S is (K with ``control_time``) -- and g = -d
+        search     sequential: trial t is clip(c + s_t dir), one forward sweep of S members with the shared control, and
+                   one fused cost pass; it stops at the first accepted trial
+        take       the S accepted trajectories become the iterate
+
+    There is no speculative mode: the scenarios are the batch, and a trial sweep is already S members wide.  State bounds
+    are not carried by this loop (``state_bounds`` raises).  S is at most ``_lib.MAX_MEMBERS``.
+
+    Returns ``(u, p, c, history)`` with u, p of shape (S, tlen); history holds the keys of lbfgs_solidbody (``sweeps``
+    counts batched sweeps) and, per accepted iterate, ``scenario_costs`` (the S values T_s), ``worst`` (their maximum over
+    the scenarios of non-zero weight) and ``control_cost`` (beta/2 ||c||^2_Q); ``scenario_costs0`` holds the T_s at ``c0``."""
+    if state_bounds is not None:
+        raise ValueError("state_bounds: state bounds are not carried by the ensemble loop (use lbfgs_solidbody per scenario)")
+    if not isinstance(scenarios, Ensemble):
+        raise ValueError("scenarios must be an Ensemble")
+    _need_obs(optim, obs)
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    levels = Nt + 1
+    S, w = scenarios.S, scenarios.weights
+    if S * 1 > _lib.MAX_MEMBERS:
+        raise ValueError(f"{S} scenarios: at most {_lib.MAX_MEMBERS} per ensemble")
+    K = int(max_armijo)
+    if K < 1:
+        raise ValueError(f"max_armijo = {max_armijo}: must be >= 1")
+    if scenarios.u0.shape[1] != n:
+        raise ValueError(f"u0 of {scenarios.u0.shape[1]} values per scenario, expected {n}")
+    hsize = n if optim == "finaltime" else tl
+    if scenarios.uhat.shape[1] != hsize:
+        raise ValueError(f"targets of {scenarios.uhat.shape[1]} values per scenario, expected {hsize} for optim='{optim}'")
+    c0 = np.asarray(c0, dtype=np.float64).ravel()
+    if c0.size != tl:
+        raise ValueError(f"c0 of {c0.size} values, expected {tl}")
+    if control_time is not None:
+        control_time.need(c0, n, Nt)
+    lm = LimitedMemory(ctx, tl, memory, dt)
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    try:
+        u, p, uB = alloc(S * tl), alloc(S * tl), alloc(S * tl)
+        d, g, rhs, cB = alloc(tl), alloc(tl), alloc(tl, False), alloc(tl)
+        c = alloc(tl, False).upload(c0)
+        qn_bufs = (alloc(tl, False), alloc(tl, False), alloc(tl, False))
+        u0d = alloc(S * n, False).upload(scenarios.u0.ravel())
+        uh = alloc(S * hsize, False).upload(scenarios.uhat.ravel())
+        for s in range(S):      # level 0 of every scenario's trajectories = its initial condition
+            u.copy_from(u0d, n, dst_off=s * tl, src_off=s * n)
+            uB.copy_from(u0d, n, dst_off=s * tl, src_off=s * n)
+        # the sweeps and the cost are the snapshot ones: final-time and all-time through their Observations corners
+        # (the final-time targets copied once to level num_steps of a trajectory-sized buffer the problem keeps)
+        ob, target = prob._corner(optim, obs, uh, S)
+        theta, cost_w, window = prob.obs_device(ob)
+        cur = dict(u=u, uB=uB)
+        stats = {}
+
+        def costs(uu, cc, cref=None):
+            return ctx.ensemble_costs(uu, target, cost_w, cc, w, beta, Nt, dt, window=window, cref=cref)
+
+        prob.forward(c, u, batch=S, c_shared=True)
+        last = costs(u, c)
+        J0 = last[1]
+
+        def gradient():
+            ctx.solidbody_adjoint_obs(prob.Arot, c, cur["u"], target, theta, ob.tau, window, p, Nt, dt, prob.eps,
+                                      prob.rot_scale, prob.drift, S, True)
+            ctx.ensemble_drift_gradient_rhs(c, cur["u"], p, w, beta, rhs, levels, prob.drift)
+            if control_time is None:
+                ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=levels)
+            else:
+                prob._projected_solve(control_time, rhs, d, 1)
+            ctx.axpby(tl, -1.0, d, 0.0, None, g)
+
+        def search(dirv, J_k, svals, margins):
+            for k, s in enumerate(svals):
+                ctx.project_control(c, s, dirv, c_lower, c_upper, cB, tl)
+                prob.forward(cB, cur["uB"], batch=S, c_shared=True)
+                T, J, dist = costs(cur["uB"], cB, cref=c)
+                t, _ = _first_accepted([J], [dist], J_k, [s], gam, margins)
+                if t is not None:
+                    stats["last"] = (T, J)
+                    return k, J, dist, k + 1
+            return None, None, None, len(svals)
+
+        def take(t):
+            c.copy_from(cB, tl)
+            cur["u"], cur["uB"] = cur["uB"], cur["u"]       # the S accepted trajectories: a swap (level 0 is the same)
+            T, J = stats["last"]
+            track = 0.0
+            for ws, Ts in zip(w[w != 0], T[w != 0]):
+                track = track + float(ws * Ts)
+            stats.setdefault("scenario_costs", []).append(T.copy())
+            stats.setdefault("worst", []).append(float(T[w != 0].max()))
+            stats.setdefault("control_cost", []).append(J - track)       # (beta/2 ||c||^2_Q up to the rounding of J)
+
+        stop = lambda J, Jt, dist: tol is not None and abs(J - Jt) / abs(J) < tol
+        hist = _lbfgs_iterate(ctx, lm, tl, c, g, qn_bufs, J0, gradient, search, take, c_lower, c_upper, int(iters), gam,
+                              s0, K, stop)
+        for key in ("scenario_costs", "worst", "control_cost"):
+            hist[key] = stats.get(key, [])
+        hist["scenario_costs0"] = last[0]
+        return (cur["u"].download().reshape(S, tl), p.download().reshape(S, tl), c.download(), hist)
+    finally:
+        lm.close()
+        for a in bufs:
+            a.free()

@@ -446,6 +446,31 @@ int femfct_l1_norm_Q(femfct_ctx* ctx, const double* a_dev, int32_t num_steps, do
 int femfct_sparse_trial_stats(femfct_ctx* ctx, const double* c_trials_dev, const double* c_ref_dev, int32_t K,
                               int32_t num_steps, double dt, double* l1_host, double* dist_host, int64_t* nnz_host);
 
+/* Ensemble drift control (solvers.ensemble_solidbody; added after ABI version 5, backward compatible; an extension without
+ * a counterpart in the reference): one control c serves S scenarios, 1 <= S <= FEMFCT_MAX_MEMBERS, each with its own state
+ * u_s, FCT adjoint p_s, target uhat_s and weight pi_s >= 0,
+ *   J(c) = sum_s pi_s T_s + beta/2 ||c||^2_Q,     T_s = femfct_obs_cost of scenario s.
+ * The limiter is nonlinear, so the weights enter where the gradient is formed and not in the adjoint loads.  weights_host:
+ * S values, read before the call returns; a negative or non-finite weight, or all weights zero, is FEMFCT_ERR_INVALID. */
+/* out_l = -(beta M c_l + acc_l) for every level l < levels, acc = pi_s0 g_s0 for the first scenario of non-zero weight, then
+ * acc = acc + pi_s g_s in index order (no contraction), g_s = assemble(p_s (b.grad u_s) v dx) row by row the expression of
+ * femfct_drift_gradient_rhs.  c_dev, out_dev: one trajectory of levels*n doubles; u_traj, p_traj: S of them, scenario s at
+ * s*levels*n.  A scenario of weight 0 is not read.  S = 1 with weight 1, and two equal scenarios with weights 1/2, give
+ * femfct_drift_gradient_rhs's bits.  One launch with that call's geometry, does not synchronise. */
+int femfct_ensemble_drift_gradient_rhs(femfct_ctx* ctx, const double* c_dev, const double* u_traj, const double* p_traj,
+                                       const double* weights_host, int32_t S, double beta, double bx, double by,
+                                       double* out_dev, int32_t levels);
+/* T_host[s] = femfct_obs_cost of scenario s (every s, weight 0 included: diagnostics), J_host[0] = (sum_s pi_s T_s, index
+ * order, non-zero weights, no contraction) + (0.5*beta) * femfct_l2_norm_sq_Q(c), dist_host[0] = femfct_l2_norm_sq_Q(c -
+ * cref), each of the three bit for bit those calls' values and independent of S.  u_traj, uhat_traj: S trajectories of
+ * (num_steps+1)*n doubles; cost_w_dev, window_dev: as femfct_obs_cost; c_dev, cref_dev: one trajectory each, the control
+ * is read once; cref_dev and dist_host are given together or both NULL.  One pass over the scenarios, one over the
+ * control, one read-back.  Synchronises. */
+int femfct_ensemble_costs(femfct_ctx* ctx, const double* u_traj, const double* uhat_traj, const double* cost_w_dev,
+                          const double* window_dev, const double* c_dev, const double* cref_dev,
+                          const double* weights_host, int32_t S, double beta, int32_t num_steps, double dt,
+                          double* T_host, double* J_host, double* dist_host);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
