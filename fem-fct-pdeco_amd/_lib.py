@@ -172,6 +172,9 @@ SIGNATURES = {
     "femfct_sparse_trial_stats": (C.c_int, [_p, _p, _p, _i, _i, _d, _p, _p, _p]),
     "femfct_ensemble_drift_gradient_rhs": (C.c_int, [_p, _p, _p, _p, _p, _i, _d, _d, _d, _p, _i]),
     "femfct_ensemble_costs": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _d, _p, _p, _p]),
+    "femfct_smooth_cost": (C.c_int, [_p, _p, _i, _d, _p, _i]),
+    "femfct_smooth_rhs": (C.c_int, [_p, _p, _d, _d, _i, _d, _p, _i]),
+    "femfct_drift_gradient_rhs_smooth": (C.c_int, [_p, _p, _p, _p, _d, _d, _d, _d, _p, _i, _d, _d]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -632,6 +632,26 @@ class Context:
             float(beta), int(num_steps), float(dt), _host_ptr(T), _host_ptr(J), None if dist is None else _host_ptr(dist)))
         return T, float(J[0]), (None if dist is None else float(dist[0]))
 
+    # -- smooth controls (solvers.Smoothness): the H1 seminorm in space and time ------------------------------
+    def smooth_cost(self, c, num_steps, dt, batch=1) -> np.ndarray:
+        """``(batch, 2)``: R_x = dt sum_l w_l c_l^T Ad c_l and R_t = 1/dt sum_l (c_{l+1} - c_l)^T M (c_{l+1} - c_l) per
+        batch member, from one pass over ``c`` with one read-back."""
+        out = np.empty((max(int(batch), 1), 2))
+        check(self.handle, lib.femfct_smooth_cost(self.handle, dptr(c), int(num_steps), float(dt), _host_ptr(out),
+                                                  int(batch)))
+        return out
+
+    def smooth_rhs(self, c, beta_x, beta_t, num_steps, dt, out, batch=1):
+        """out_l = -(beta_x Ad c_l + beta_t M tau_l) for every level and batch member, one launch."""
+        check(self.handle, lib.femfct_smooth_rhs(self.handle, dptr(c), float(beta_x), float(beta_t), int(num_steps),
+                                                 float(dt), dptr(out), int(batch)))
+
+    def drift_gradient_rhs_smooth(self, c, u, p, beta, beta_x, beta_t, dt, out, levels, drift=(1.0, 1.0)):
+        """``drift_gradient_rhs`` + ``smooth_rhs`` in one launch, bit for bit their sum."""
+        check(self.handle, lib.femfct_drift_gradient_rhs_smooth(
+            self.handle, dptr(c), dptr(u), dptr(p), float(beta), float(beta_x), float(beta_t), float(dt), dptr(out),
+            int(levels), float(drift[0]), float(drift[1])))
+
     # -- non-FCT species / PDE systems ---------------------------------------------------
     def descent_pointwise(self, count, beta, c, x, out, y=None, scale=1.0, divisor=1.0):
         """out = -(beta*c - t), t = x*y/divisor (y given) or scale*x"""

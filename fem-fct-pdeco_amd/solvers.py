@@ -225,6 +225,33 @@ class StateBounds:
         return self
 
 
+class Smoothness:
+    """H1 regularisation of a control trajectory c = (c_0 .. c_Nt) in space and time, on top of beta/2 ||c||^2_Q:
+
+        R(c) = beta_x/2 R_x + beta_t/2 R_t
+        R_x  = dt sum_{l=0..Nt} w_l c_l^T Ad c_l                          (the trapezoid's w, Ad = assemble(grad u . grad v dx))
+        R_t  = 1/dt sum_{l<Nt} (c_{l+1} - c_l)^T M (c_{l+1} - c_l)        (M the consistent mass of ``l2_norm_sq_Q``)
+
+    the discrete beta_x/2 int int |grad c|^2 + beta_t/2 int int (dc/dt)^2.  Its gradient in the inner product of
+    ``l2_norm_sq_Q`` has the per-level form of beta M c_l, M g_l = beta_x Ad c_l + beta_t M tau_l with the three-point
+    time stencil tau (``femfct_smooth_rhs``), so a direction stays one mass solve per level.  Both coefficients finite
+    and >= 0; ``Smoothness(0, 0)`` leaves every iterate as it is and only records the roughness."""
+
+    def __init__(self, beta_x=0.0, beta_t=0.0):
+        self.beta_x, self.beta_t = float(beta_x), float(beta_t)
+        for name, b in (("beta_x", self.beta_x), ("beta_t", self.beta_t)):
+            if not (np.isfinite(b) and b >= 0.0):
+                raise ValueError(f"{name} = {b}: must be finite and >= 0")
+
+    @property
+    def active(self):
+        return self.beta_x != 0.0 or self.beta_t != 0.0
+
+    def value(self, Rx, Rt):
+        """R = beta_x/2 Rx + beta_t/2 Rt"""
+        return self.beta_x / 2 * Rx + self.beta_t / 2 * Rt
+
+
 def _need_obs(optim, obs):
     if optim not in OPTIMS:
         raise ValueError(f"Invalid value for 'optim': '{optim}'. Must be one of {list(OPTIMS)}.")
@@ -438,16 +465,22 @@ class SolidBodyDrift:
         self.ctx.solidbody_adjoint(self.Arot, c, u, uhat, p, self.num_steps, self.dt, self.eps, self.rot_scale,
                                    self.drift, optim == "alltime", self.batch if batch is None else batch, c_shared)
 
-    def descent_direction(self, c, u, p, beta, d, scratch=None, control_time=None):
+    def descent_direction(self, c, u, p, beta, d, scratch=None, control_time=None, smoothness=None):
         """d_k = ChebSI(-(beta*M*c_k + int p_k (b.grad u_k) v)) for every level k (finaltime.py:228-238);
         all levels are one batched launch sequence.  ``control_time`` (a :class:`ControlIntervals`): the direction
         projected onto the controls constant on its K intervals.  The projection commutes with the per-level mass solve,
-        so the right-hand sides are restricted first and K systems are solved in place of num_steps + 1."""
+        so the right-hand sides are restricted first and K systems are solved in place of num_steps + 1.
+        ``smoothness`` (a :class:`Smoothness`): the right-hand side gains -(beta_x Ad c_k + beta_t M tau_k) in the same
+        launch; the restriction acts on the right-hand side, so it composes with ``control_time`` unchanged."""
         levels = self.num_steps + 1
         own = scratch is None
         rhs = self.ctx.empty(self.tlen) if own else scratch
         try:
-            self.ctx.drift_gradient_rhs(c, u, p, beta, rhs, levels, self.drift)
+            if smoothness is None:
+                self.ctx.drift_gradient_rhs(c, u, p, beta, rhs, levels, self.drift)
+            else:
+                self.ctx.drift_gradient_rhs_smooth(c, u, p, beta, smoothness.beta_x, smoothness.beta_t, self.dt, rhs,
+                                                   levels, self.drift)
             if control_time is None:
                 self.ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=levels)
             else:
@@ -473,8 +506,14 @@ class SolidBodyDrift:
             buf = self.__dict__["_ivl_buf"] = self.ctx.empty(count)
         return buf.ptr, buf.ptr + 8 * (count // 2)
 
-    def cost(self, u, target, c, beta, optim, batch=None, obs=None, state_bounds=None):
-        """J per batch member.  ``state_bounds``: J + P, the statistics of the pass kept in ``last_bound_stats``."""
+    def cost(self, u, target, c, beta, optim, batch=None, obs=None, state_bounds=None, smoothness=None):
+        """J per batch member.  ``state_bounds``: J + P, the statistics of the pass kept in ``last_bound_stats``.
+        ``smoothness``: J + R, ``(R_x, R_t)`` of every member from one fused pass kept in ``last_smooth_stats``."""
+        if smoothness is not None:
+            J = self.cost(u, target, c, beta, optim, batch=batch, obs=obs, state_bounds=state_bounds)
+            st = self.ctx.smooth_cost(c, self.num_steps, self.dt, batch=self.batch if batch is None else batch)
+            self.last_smooth_stats = st
+            return J + smoothness.value(st[:, 0], st[:, 1])
         if state_bounds is not None:
             return self.cost(u, target, c, beta, optim, batch=batch, obs=obs) + self.bound_stats(u, state_bounds, batch)[0]
         if _need_obs(optim, obs):       # every member (all Armijo trials of a batched sweep) in one call
@@ -548,10 +587,22 @@ class LinearSourceControl(SolidBodyDrift):
         """:259-274 (all-time) / advection_FCT_PDECO_finaltime.py (final-time)"""
         self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True, obs=obs, state_bounds=state_bounds)
 
-    def descent_direction(self, c, p, beta, d, control_time=None):
+    def descent_direction(self, c, p, beta, d, control_time=None, smoothness=None):
         """advection_FCT_PDECO_alltime_exact.py:278: d = -(beta*c - p), every level, the script's operation order.
-        ``control_time`` (a :class:`ControlIntervals`): then projected onto the controls constant on its intervals."""
-        self.ctx.descent_pointwise(self.tlen, beta, c, p, d)
+        ``control_time`` (a :class:`ControlIntervals`): then projected onto the controls constant on its intervals.
+        ``smoothness`` (a :class:`Smoothness` with a non-zero coefficient): d = -(beta*c - p) + ChebSI(smooth_rhs), one
+        mass solve per level for the term's gradient, before the projection."""
+        if smoothness is not None and smoothness.active:
+            buf = self.__dict__.get("_smooth_buf")
+            if buf is None:
+                buf = self.__dict__["_smooth_buf"] = self.ctx.empty(2 * self.tlen)
+            rhs, sm = buf.ptr, buf.ptr + 8 * self.tlen
+            self.ctx.smooth_rhs(c, smoothness.beta_x, smoothness.beta_t, self.num_steps, self.dt, rhs, batch=1)
+            self.ctx.chebsi(rhs, sm, 20, 0.5, 2.0, batch=self.num_steps + 1)
+            self.ctx.descent_pointwise(self.tlen, beta, c, p, rhs)
+            self.ctx.axpby(self.tlen, 1.0, rhs, 1.0, sm, d)
+        else:
+            self.ctx.descent_pointwise(self.tlen, beta, c, p, d)
         if control_time is not None:
             K = control_time.check(self.num_steps).K
             self.ctx.time_project(d, control_time.starts, self.num_steps, self._interval_fields(2 * K * self.n)[0])
@@ -693,35 +744,52 @@ def _record_bounds(prob, hist, member):
     hist.setdefault("violated_fraction", []).append(float(frac))
 
 
+def _smooth_kw(smoothness):
+    """the keyword the loops pass on to ``prob.descent_direction`` / ``prob.cost`` (none without the term: today's calls)"""
+    if smoothness is None:
+        return {}
+    if not isinstance(smoothness, Smoothness):
+        raise ValueError("smoothness must be a Smoothness")
+    return dict(smoothness=smoothness)
+
+
+def _record_smooth(prob, hist, member):
+    """``(R_x, R_t)`` of batch member ``member`` of the last cost pass, the accepted iterate's, into the history"""
+    Rx, Rt = prob.last_smooth_stats[member]
+    hist.setdefault("roughness_x", []).append(float(Rx))
+    hist.setdefault("roughness_t", []).append(float(Rt))
+
+
 def pgd_solidbody_finaltime(prob: SolidBodyDrift, u0, uhat_T, c0, beta, c_lower, c_upper, iters,
                             gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
-                            state_bounds=None):
+                            state_bounds=None, smoothness=None):
     """Final-time variant of :func:`pgd_solidbody` (advection_solidbody_FCT_PDECO_finaltime_Garvie.py)."""
     return pgd_solidbody(prob, u0, uhat_T, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="finaltime", control_time=control_time, state_bounds=state_bounds)
+                         optim="finaltime", control_time=control_time, state_bounds=state_bounds, smoothness=smoothness)
 
 
 def pgd_solidbody_alltime(prob: SolidBodyDrift, u0, uhat_all, c0, beta, c_lower, c_upper, iters,
                           gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
-                          state_bounds=None):
+                          state_bounds=None, smoothness=None):
     """All-time variant (advection_solidbody_FCT_PDECO_alltime_Garvie.py, config C5's loop): ``uhat_all``
     is the target trajectory ((Nt+1)*n, level 0 = u0)."""
     return pgd_solidbody(prob, u0, uhat_all, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="alltime", control_time=control_time, state_bounds=state_bounds)
+                         optim="alltime", control_time=control_time, state_bounds=state_bounds, smoothness=smoothness)
 
 
 def pgd_solidbody_snapshots(prob: SolidBodyDrift, u0, uhat, obs: Observations, c0, beta, c_lower, c_upper, iters,
                             gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
-                            state_bounds=None):
+                            state_bounds=None, smoothness=None):
     """Snapshot variant of :func:`pgd_solidbody`: ``uhat`` is a (num_steps+1)*n trajectory of which only the levels that
     ``obs`` observes are read (the others may hold anything, NaN included)."""
     return pgd_solidbody(prob, u0, uhat, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="snapshots", obs=obs, control_time=control_time, state_bounds=state_bounds)
+                         optim="snapshots", obs=obs, control_time=control_time, state_bounds=state_bounds,
+                         smoothness=smoothness)
 
 
 def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters,
                   gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None,
-                  control_time=None, state_bounds=None):
+                  control_time=None, state_bounds=None, smoothness=None):
     """Projected gradient descent for the drift-control problem, following the loop of
     advection_solidbody_FCT_PDECO_finaltime_Garvie.py:164-330 / ..._alltime_Garvie.py:164-340 step for step:
 
@@ -742,9 +810,13 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     these controls and ``c0`` must be one of them (ValueError otherwise).  None: the free space-time control.
     ``state_bounds`` (a :class:`StateBounds`): the loop descends J + P, and the history gains ``penalty``,
     ``max_violation`` and ``violated_fraction`` of the accepted iterate, from the pass that costs the trials.
+    ``smoothness`` (a :class:`Smoothness`): the loop descends J + R (+ P), the direction's right-hand side gains the
+    term's in the same launch, and the history gains ``roughness_x`` and ``roughness_t``, R_x and R_t of the accepted
+    iterate, from the pass that costs the trials.
     Returns ``(u, p, c, history)`` as NumPy arrays + a dict of per-iteration scalars."""
     snap = _need_obs(optim, obs)
     sbk = _bounds_kw(prob, state_bounds)
+    smk = _smooth_kw(smoothness)
     alltime = optim == "alltime" or snap         # (the target is a trajectory)
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     if control_time is not None:
@@ -780,12 +852,12 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
         for it in range(iters):
             prob.adjoint(c_prev, u, uh, p, optim, batch=1, obs=obs, **sbk)
             if control_time is None:
-                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs)
+                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, **smk)
             else:
-                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, control_time=control_time)
+                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, control_time=control_time, **smk)
             ctx.project_control(c_prev, s0, d, c_lower, c_upper, c, tl)
             prob.forward(c, u, batch=1)
-            J_k = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs, **sbk)[0])
+            J_k = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs, **sbk, **smk)[0])
             svals = [s0 * (1 / 2 ** k) for k in range(max_armijo)]
             accepted = None
             if speculative:
@@ -793,7 +865,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
                     ctx.project_control(c, s, d, c_lower, c_upper, cB.ptr + 8 * k * tl, tl)
                     ckB.copy_from(c, tl, dst_off=k * tl)
                 prob.forward(cB, uB, batch=B)
-                J = prob.cost(uB, uhB, cB, beta, optim, batch=B, obs=obs, **sbk)
+                J = prob.cost(uB, uhB, cB, beta, optim, batch=B, obs=obs, **sbk, **smk)
                 stat = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=B)
                 margins = []
                 for k, s in enumerate(svals):
@@ -810,7 +882,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
                     accepted = k
                     ctx.project_control(c, s, d, c_lower, c_upper, cB, tl)
                     prob.forward(cB, uB, batch=1)
-                    J_acc = float(prob.cost(uB, uh, cB, beta, optim, batch=1, obs=obs, **sbk)[0])
+                    J_acc = float(prob.cost(uB, uh, cB, beta, optim, batch=1, obs=obs, **sbk, **smk)[0])
                     stat = float(ctx.l2_norm_sq_Q(cB, c, Nt, dt)[0])
                     margins.append((J_acc - J_k + gam / s * stat) / abs(J_k))
                     if not (J_acc - J_k > -gam / s * stat):
@@ -819,6 +891,8 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
                 u.copy_from(uB, tl)
             if sbk:
                 _record_bounds(prob, hist, accepted if speculative else 0)
+            if smk:
+                _record_smooth(prob, hist, accepted if speculative else 0)
             hist["cost"].append(J_acc)
             hist["wall"].append(time.perf_counter())          # (J_acc is a read-back: the iteration's device work is done)
             hist["armijo_margin"].append(margins)
@@ -1004,7 +1078,7 @@ def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c
 
 def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
                        increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
-                       control_time=None, state_bounds=None):
+                       control_time=None, state_bounds=None, smoothness=None):
     """Projected gradient descent for the linear source-control problem, the loop of
     advection_FCT_PDECO_alltime_exact.py:212-330 (optim="alltime", stop="both") and advection_FCT_PDECO_finaltime.py:
     170-280 (optim="finaltime", stop="cost"):
@@ -1031,10 +1105,17 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
     J(S(g + c_k), c_k) of the re-solved state at the control iteration k started from, so hist["cost_state"][k + 1]
     re-solves hist["cost"][k].
     ``state_bounds`` (a :class:`StateBounds`; increment="resolve" only): the loop descends J + P, and the history gains
-    ``penalty``, ``max_violation`` and ``violated_fraction`` of the accepted iterate."""
+    ``penalty``, ``max_violation`` and ``violated_fraction`` of the accepted iterate.
+    ``smoothness`` (a :class:`Smoothness`; increment="resolve" only): the loop descends J + R (+ P) with
+    d = -(beta c_k - p) + ChebSI(smooth_rhs), and the history gains ``roughness_x`` and ``roughness_t`` of the accepted
+    iterate."""
     snap = _need_obs(optim, obs)
     if increment not in ("linear", "resolve"):
         raise ValueError(f"Invalid value for 'increment': '{increment}'. Must be one of ['linear', 'resolve'].")
+    if smoothness is not None and increment == "linear":
+        raise ValueError("smoothness needs increment='resolve': the fused linear-increment trial costs do not know the "
+                         "term")
+    smk = _smooth_kw(smoothness)
     if state_bounds is not None and increment == "linear":
         raise ValueError("state_bounds needs increment='resolve': the fused linear-increment trial costs know the "
                          "all-time and final-time modes only")
@@ -1083,7 +1164,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             for k in range(K):
                 uB.copy_from(u, n, dst_off=k * tl)              # level 0 of every trial state = u0
                 uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
-        cost = lambda uu, cc: float(prob.cost(uu, uh, cc, beta, optim, batch=1, obs=obs, **sbk)[0])
+        cost = lambda uu, cc: float(prob.cost(uu, uh, cc, beta, optim, batch=1, obs=obs, **sbk, **smk)[0])
         J_ref = 10 * cost(u, c)                                 # alltime_exact.py:212 / finaltime.py:170
         hist = dict(cost=[], cost_state=[], armijo_k=[], step=[], stop_crit=[], stop_crit2=[], armijo_margin=[],
                     wall=[], wall0=time.perf_counter())
@@ -1099,16 +1180,16 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             else:
                 prob.adjoint_state(u, uh, p, optim, batch=1)
             if control_time is None:
-                prob.descent_direction(c, p, beta, d)
+                prob.descent_direction(c, p, beta, d, **smk)
             else:
-                prob.descent_direction(c, p, beta, d, control_time=control_time)
+                prob.descent_direction(c, p, beta, d, control_time=control_time, **smk)
             if linear:
                 prob.sensitivity(d, w)
                 J, dist = ctx.linear_trial_costs(u, w, uh, c, d, s0, K, c_lower, c_upper, beta, Nt, dt, optim)
             else:
                 ctx.source_trials(c, d, s0, K, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
                 prob.state(srcB, uB, batch=K)
-                J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs, **sbk)
+                J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs, **sbk, **smk)
                 for k in range(K):
                     ckB.copy_from(c, tl, dst_off=k * tl)
                 dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=K)
@@ -1121,6 +1202,8 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
             J_acc, dist_acc = float(J[acc]), float(dist[acc])
             if sbk:
                 _record_bounds(prob, hist, acc)
+            if smk:
+                _record_smooth(prob, hist, acc)
             nc = float(ctx.l2_norm_sq_Q(c, None, Nt, dt)[0])
             stop1 = dist_acc / nc if nc > 0 else np.inf
             stop2 = abs(J_ref - J_acc) / abs(J_ref)
@@ -1324,7 +1407,7 @@ def _first_accepted(J, dist, J_k, svals, gam, margins):
 
 def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters, memory=5, gam=1e-4, s0=1.0,
                     max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None, control_time=None,
-                    state_bounds=None):
+                    state_bounds=None, smoothness=None):
     """Projected L-BFGS descent for the drift-control problem: the sweeps, cost, direction kernels and Armijo test of
     :func:`pgd_solidbody` with the direction of a :class:`LimitedMemory` of ``memory`` pairs.  Per iteration, at the
     control c with u = S(c) and J = J(u, c):
@@ -1338,13 +1421,15 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
     loop, not a restatement of a script), so an accepted cost never exceeds the previous one.  ``memory=0`` is plain
     projected gradient with this search.  ``speculative=True`` evaluates the ``max_armijo`` trials as one batch, as
     pgd_solidbody does.  With ``control_time`` s, y, g and the free set are constant on every interval, so the iterates
-    stay piecewise constant bit for bit.  ``optim``, ``obs``, ``tol``, ``state_bounds``: as in pgd_solidbody.
+    stay piecewise constant bit for bit.  ``optim``, ``obs``, ``tol``, ``state_bounds``, ``smoothness``: as in
+    pgd_solidbody.
 
     Returns ``(u, p, c, history)``; history: ``cost``, ``armijo_k``, ``armijo_margin`` (every trial looked at, the
     quasi-Newton ones first), ``used`` ("qn" / "g"), ``pairs``, ``free_fraction``, ``sweeps`` (state and adjoint sweeps so
     far, counting the trials a sequential search looks at), ``step``, ``rel_change``, ``wall``, ``cost0``, ``stalled``."""
     snap = _need_obs(optim, obs)
     sbk = _bounds_kw(prob, state_bounds)
+    smk = _smooth_kw(smoothness)
     alltime = optim == "alltime" or snap
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     K = int(max_armijo)
@@ -1382,7 +1467,7 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
         for k in range(B):
             uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
             uB.copy_from(u0d, n, dst_off=k * tl)          # level 0 of every trial trajectory = the initial condition
-        cost = lambda uu, hh, cc, b: prob.cost(uu, hh, cc, beta, optim, batch=b, obs=obs, **sbk)
+        cost = lambda uu, hh, cc, b: prob.cost(uu, hh, cc, beta, optim, batch=b, obs=obs, **sbk, **smk)
         prob.forward(c, u, batch=1)
         J0 = float(cost(u, uh, c, 1)[0])
         bstat = {}
@@ -1390,9 +1475,9 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
         def gradient():
             prob.adjoint(c, u, uh, p, optim, batch=1, obs=obs, **sbk)
             if control_time is None:
-                prob.descent_direction(c, u, p, beta, d, scratch=rhs)
+                prob.descent_direction(c, u, p, beta, d, scratch=rhs, **smk)
             else:
-                prob.descent_direction(c, u, p, beta, d, scratch=rhs, control_time=control_time)
+                prob.descent_direction(c, u, p, beta, d, scratch=rhs, control_time=control_time, **smk)
             ctx.axpby(tl, -1.0, d, 0.0, None, g)
 
         def search(dirv, J_k, svals, margins):
@@ -1421,6 +1506,8 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
             u.copy_from(uB, tl, src_off=off)
             if sbk:         # (the last cost pass is that of the search that found t)
                 _record_bounds(prob, bstat, t if speculative else 0)
+            if smk:
+                _record_smooth(prob, bstat, t if speculative else 0)
 
         stop = lambda J, Jt, dist: tol is not None and abs(J - Jt) / abs(J) < tol
         hist = _lbfgs_iterate(ctx, lm, tl, c, g, qn_bufs, J0, gradient, search, take, c_lower, c_upper, int(iters), gam,
@@ -1435,7 +1522,7 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
 
 def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
                          memory=5, gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
-                         control_time=None, state_bounds=None):
+                         control_time=None, state_bounds=None, smoothness=None):
     """Projected L-BFGS descent for the linear source-control problem (:class:`LinearSourceControl`,
     :class:`LinearReactionSourceControl`): the iteration of :func:`lbfgs_solidbody` with the gradient
     -descent_direction = beta c - p, the trial controls and sources of ``femfct_source_trials`` and the ``max_armijo``
@@ -1443,9 +1530,11 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
     compares with the cost of the current iterate, J(S(g + c_k), c_k) (no unconditional first step and no 10 J start
     value).  The loop runs while stop_crit2 = |J_k - J_acc| / |J_k| >= tol, or (stop="both")
     stop_crit = ||c_{k+1} - c_k||^2_Q / ||c_k||^2_Q >= tol, and fewer than ``max_iters`` iterations have run.
-    Arguments and return value as pgd_source_control; the history is lbfgs_solidbody's with ``stop_crit``, ``stop_crit2``."""
+    Arguments (``smoothness`` included) and return value as pgd_source_control; the history is lbfgs_solidbody's with
+    ``stop_crit``, ``stop_crit2``."""
     snap = _need_obs(optim, obs)
     sbk = _bounds_kw(prob, state_bounds)
+    smk = _smooth_kw(smoothness)
     if stop not in ("both", "cost"):
         raise ValueError(f"Invalid value for 'stop': '{stop}'. Must be one of ['both', 'cost'].")
     K = int(max_armijo)
@@ -1489,7 +1578,7 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
         if gd is not None:
             ctx.axpby(tl, 1.0, gd, 1.0, c, src)
         prob.state(src, u, batch=1)
-        J0 = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs, **sbk)[0])
+        J0 = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs, **sbk, **smk)[0])
         crit = dict(stop_crit=[], stop_crit2=[])
 
         def gradient():
@@ -1498,15 +1587,15 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
             else:
                 prob.adjoint_state(u, uh, p, optim, batch=1)
             if control_time is None:
-                prob.descent_direction(c, p, beta, d)
+                prob.descent_direction(c, p, beta, d, **smk)
             else:
-                prob.descent_direction(c, p, beta, d, control_time=control_time)
+                prob.descent_direction(c, p, beta, d, control_time=control_time, **smk)
             ctx.axpby(tl, -1.0, d, 0.0, None, gr)
 
         def search(dirv, J_k, svals, margins):
             ctx.source_trials(c, dirv, s0, K, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
             prob.state(srcB, uB, batch=K)
-            J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs, **sbk)
+            J = prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs, **sbk, **smk)
             for k in range(K):
                 ckB.copy_from(c, tl, dst_off=k * tl)
             dist = ctx.l2_norm_sq_Q(cB, ckB, Nt, dt, batch=K)
@@ -1518,6 +1607,8 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
             u.copy_from(uB, tl, src_off=t * tl)
             if sbk:
                 _record_bounds(prob, crit, t)
+            if smk:
+                _record_smooth(prob, crit, t)
 
         def stop_test(J, Jt, dist):
             nc = float(ctx.l2_norm_sq_Q(qn_bufs[1], None, Nt, dt)[0])      # (c_old: the control the step started from)

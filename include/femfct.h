@@ -471,6 +471,32 @@ int femfct_ensemble_costs(femfct_ctx* ctx, const double* u_traj, const double* u
                           const double* weights_host, int32_t S, double beta, int32_t num_steps, double dt,
                           double* T_host, double* J_host, double* dist_host);
 
+/* Smooth controls (solvers.Smoothness; added after ABI version 5, backward compatible; an extension without a counterpart
+ * in the reference): the H1 seminorm of a control trajectory c = (c_0 .. c_Nt) in space and time,
+ *   R(c) = beta_x/2 R_x + beta_t/2 R_t,    R_x = dt sum_{l=0..Nt} w_l c_l^T Ad c_l,
+ *                                          R_t = (1/dt) sum_{l<Nt} (c_{l+1} - c_l)^T M (c_{l+1} - c_l),
+ * w the trapezoid's level weights (1/2 at the end levels), Ad = femfct_stiffness_ell, M the mass of femfct_l2_norm_sq_Q.
+ * Its gradient g in that call's inner product (dR(c)[v] = dt sum_l w_l g_l^T M v_l) satisfies
+ *   M g_l = beta_x Ad c_l + beta_t M tau_l,   tau_l = (2 c_l - c_{l-1} - c_{l+1})/dt^2 for 0 < l < Nt,
+ *   tau_0 = 2 (c_0 - c_1)/dt^2,  tau_Nt = 2 (c_Nt - c_{Nt-1})/dt^2.
+ * All three need the structured mesh (femfct_set_mesh_square), num_steps >= 1, dt > 0 and finite coefficients >= 0
+ * (FEMFCT_ERR_INVALID otherwise); no atomics, fixed summation trees: two calls return the same bits. */
+/* out_host[2 b] = R_x, out_host[2 b + 1] = R_t of batch member b (not scaled by the coefficients); c_dev: batch
+ * trajectories of (num_steps+1)*n doubles.  One pass over c, two level folds, one read-back; levels * batch is not limited.
+ * Synchronises. */
+int femfct_smooth_cost(femfct_ctx* ctx, const double* c_dev, int32_t num_steps, double dt, double* out_host, int32_t batch);
+/* out_l = -(beta_x (Ad c_l) + beta_t (M tau_l)) for every level and batch member, the right-hand side of the mass solve
+ * that gives -g.  beta_t == 0: no neighbouring level is read; beta_x == 0: Ad is not read.  out_dev must not alias c_dev.
+ * One launch, does not synchronise. */
+int femfct_smooth_rhs(femfct_ctx* ctx, const double* c_dev, double beta_x, double beta_t, int32_t num_steps, double dt,
+                      double* out_dev, int32_t batch);
+/* out_l = femfct_drift_gradient_rhs(c, u, p, beta, bx, by)_l + femfct_smooth_rhs(c, beta_x, beta_t)_l in one launch, bit for
+ * bit the sum femfct_axpby(1, ., 1, .) forms of the two; beta_x == beta_t == 0: femfct_drift_gradient_rhs's bits.
+ * levels = num_steps + 1 >= 2; one trajectory each.  Does not synchronise. */
+int femfct_drift_gradient_rhs_smooth(femfct_ctx* ctx, const double* c_dev, const double* u_dev, const double* p_dev,
+                                     double beta, double beta_x, double beta_t, double dt, double* out_dev, int32_t levels,
+                                     double bx, double by);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
