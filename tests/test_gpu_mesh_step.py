@@ -1,7 +1,12 @@
 """The one-workgroup-per-trajectory step (csrc/kernels_mesh.hip: meshes with N <= 42 nodes per side in vertex order, the
 default there; 81 x 81 from 64 trajectories per launch on) through the C ABI (-m gpu): against the tile path it replaces (FEMFCT_MESH_STEP=0) on the same inputs,
 against the CPU oracle, and its own invariants (batched == single bitwise, graphs on/off bitwise).  The systems of
-configs 3 / 4 meet the oracle through this kernel in tests/test_gpu_fullsize.py and tests/test_gpu_systems.py."""
+configs 3 / 4 meet the oracle through this kernel in tests/test_gpu_fullsize.py and tests/test_gpu_systems.py.
+
+The trajectories here run the fused step end and the graph path of the kernel, compared in relative l2 over whole
+trajectories, at every size of tests/mesh_sizes_cases.py.  tests/test_gpu_mesh_sizes.py holds single steps at those
+sizes to the oracle node by node (corners, sides, ring and interior blocks apart), with and without a non-flux matrix,
+and looks for stray writes."""
 import importlib
 
 import numpy as np
@@ -67,12 +72,15 @@ def _run(hp, solvers, monkeypatch, mesh_step, nc, Nt, B, eps, seed=7, graphs=Tru
 
 
 @pytest.mark.parametrize("eps", [0.0, 2e-3])
-@pytest.mark.parametrize("nc", [4, 11, 25, 40, 41])
+@pytest.mark.parametrize("nc", [4, 5, 6, 7, 11, 18, 19, 25, 32, 33, 34, 35, 38, 39, 40, 41])
 def test_mesh_step_matches_the_tile_path(hp, solvers, monkeypatch, nc, eps):
     """Forward sweep with a source term + all-time adjoint, 3 trajectories per launch, random controls, with and without
     physical diffusion; N = 5, 12 (even: every node of every 2 x 2 block in the mesh), 26, 41 (config meshes: own
-    instantiation), 42 (the largest that fits).  The two paths solve the low-order system to the same tolerance with
-    different iterations (block Gauss-Seidel vs Jacobi)."""
+    instantiation), 42 (the largest that fits), and the sizes of tests/mesh_sizes_cases.py at which the kernel's thread
+    layout changes: N = 6, 7, 8 (one and four interior blocks), 19, 20 (the interior fills one wave exactly), 33, 34 (the
+    ring fills one wave exactly), 35, 36 (the interior fills four waves exactly), 39, 40 (the largest odd and even N on the
+    run-time-N instantiations).  The two paths solve the low-order system to the same tolerance with different
+    iterations (block Gauss-Seidel vs Jacobi)."""
     Nt, B = 6, 3
     r1, u1, p1, log1 = _run(hp, solvers, monkeypatch, True, nc, Nt, B, eps)
     r0, u0, p0, log0 = _run(hp, solvers, monkeypatch, False, nc, Nt, B, eps)

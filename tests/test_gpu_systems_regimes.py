@@ -3,6 +3,12 @@
 The drop-in wrappers run the nonlinear, Schnakenberg and chemotaxis sweeps in vertex order (systems._system), where the
 mesh size and the batch pick the kernels of the FCT step (femfct_kernel_regime) and of the species (non-FCT) solve:
 
+  N = 6, B = 1       one-workgroup FCT step; n = 36: fewer nodes than one wave of the 1024-thread one-workgroup species
+                     solve (k_mesh_cheb_solve<2>: thread t owns the nodes t and t + 1024)
+  N = 32, B = 3      one-workgroup FCT step; n = 1024: the species solve's second node slot wholly empty
+  N = 33, B = 1      one-workgroup FCT step at an odd N with a non-flux matrix; n = 1089: 65 threads own a second node
+  N = 43, B = 1      smallest mesh on the 32-patch FCT step, species solve still one workgroup
+  N = 45, B = 1 / 8  n = 2025: the largest one-workgroup species solve, 23 threads without a second node
   N = 46, B = 1      smallest mesh past the one-workgroup species solve (n <= 2048): tile Chebyshev, 32-patch FCT step
   N = 47, B = 8      single-patch species solve (N <= 48 and B >= 8: femfct_single_patch), 32-patch FCT step
   N = 61, B = 1 / 5  32-patch tiles; 61 is no multiple of any tile width.  femfct_tile_plan takes the fewest launches for
@@ -34,6 +40,12 @@ DT = {"nonlinear": 1e-3, "schnak": 5e-4, "chtxs": 5e-4}
 
 
 CASES = [
+    pytest.param(6, 1, "MESH", {}, id="N6-B1"),
+    pytest.param(32, 3, "MESH", {}, id="N32-B3-second-slot-empty"),
+    pytest.param(33, 1, "MESH", {}, id="N33-B1-second-slot-65"),
+    pytest.param(43, 1, "TILE32", {}, id="N43-B1"),
+    pytest.param(45, 1, "TILE32", {}, id="N45-B1-largest-one-workgroup-species"),
+    pytest.param(45, 8, "TILE32", {}, id="N45-B8-largest-one-workgroup-species"),
     pytest.param(46, 1, "TILE32", {}, id="N46-B1"),
     pytest.param(47, 8, "TILE32", {}, id="N47-B8-single-patch"),
     pytest.param(61, 1, "TILE32", {}, id="N61-B1-deep-halo"),
