@@ -172,6 +172,10 @@ SIGNATURES = {
     "femfct_sparse_trial_stats": (C.c_int, [_p, _p, _p, _i, _i, _d, _p, _p, _p]),
     "femfct_ensemble_drift_gradient_rhs": (C.c_int, [_p, _p, _p, _p, _p, _i, _d, _d, _d, _p, _i]),
     "femfct_ensemble_costs": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _d, _p, _p, _p]),
+    "femfct_initial_trials": (C.c_int, [_p, _p, _p, _p, _i, _d, _d, _p, _i]),
+    "femfct_initial_trial_stats": (C.c_int, [_p, _p, _p, _p, _i, _i, _p]),
+    "femfct_initial_gradient": (C.c_int, [_p, _p, _p, _p, _d, _p, _d, _d, _p]),
+    "femfct_omega_gram": (C.c_int, [_p, _p, _i, _p, _p]),
     "femfct_smooth_cost": (C.c_int, [_p, _p, _i, _d, _p, _i]),
     "femfct_smooth_rhs": (C.c_int, [_p, _p, _d, _d, _i, _d, _p, _i]),
     "femfct_drift_gradient_rhs_smooth": (C.c_int, [_p, _p, _p, _p, _d, _d, _d, _d, _p, _i, _d, _d]),

@@ -632,6 +632,38 @@ class Context:
             float(beta), int(num_steps), float(dt), _host_ptr(T), _host_ptr(J), None if dist is None else _host_ptr(dist)))
         return T, float(J[0]), (None if dist is None else float(dist[0]))
 
+    # -- initial-state recovery (solvers.initial_state_solidbody): one-level fields of n values ------------------
+    def initial_trials(self, v, direction, steps, v_lower, v_upper, u_traj, num_steps):
+        """Level 0 of member k of the batch ``u_traj`` (K = len(steps) trajectories of ``(num_steps + 1) * n`` doubles)
+        = clip(v + steps[k] * direction, v_lower, v_upper), bitwise the NumPy expression; no other level is touched.  One
+        launch, does not synchronise."""
+        s = _as_f64(steps).reshape(-1)
+        check(self.handle, lib.femfct_initial_trials(self.handle, dptr(v), dptr(direction), _host_ptr(s), int(s.size),
+                                                     float(v_lower), float(v_upper), dptr(u_traj), int(num_steps)))
+
+    def initial_trial_stats(self, u_traj, v, K, num_steps, vb=None) -> np.ndarray:
+        """``(K, 2)``: ||v_k - vb||^2_M and ||v_k - v||^2_M for v_k = level 0 of member k of ``u_traj`` (``vb`` None: a
+        zero background), each ``l2_norm_sq_Omega`` bit for bit, from one pass with one read-back."""
+        out = np.empty((max(int(K), 1), 2))
+        check(self.handle, lib.femfct_initial_trial_stats(self.handle, dptr(u_traj), dptr(v), dptr(vb), int(K),
+                                                          int(num_steps), _host_ptr(out)))
+        return out
+
+    def initial_gradient(self, p_traj, v, beta0, g, vb=None, v_lower=0.0, v_upper=0.0, mask=None):
+        """g = beta0 * (v - vb) - p_0 (``vb`` None: 0), p_0 = level 0 of ``p_traj``; bitwise the NumPy expression.
+        ``mask`` (n bytes on the device): the free set of ``free_set(v, g, v_lower, v_upper)`` from the same launch."""
+        check(self.handle, lib.femfct_initial_gradient(self.handle, dptr(p_traj), dptr(v), dptr(vb), float(beta0), dptr(g),
+                                                       float(v_lower), float(v_upper), dptr(mask)))
+
+    def omega_gram(self, fields, mask=None) -> np.ndarray:
+        """The (J, J) Gram matrix of the one-level ``fields`` in the inner product a^T M b of ``l2_norm_sq_Omega``, each
+        masked to the free set ``mask`` (n bytes as ``free_set`` writes them; None: all free).  Exactly symmetric, the
+        same bits on every call; without a mask the diagonal is ``l2_norm_sq_Omega`` bit for bit."""
+        ptrs, J = self._fields(fields)
+        G = np.empty((J, J))
+        check(self.handle, lib.femfct_omega_gram(self.handle, ptrs, J, dptr(mask), _host_ptr(G)))
+        return G
+
     # -- smooth controls (solvers.Smoothness): the H1 seminorm in space and time ------------------------------
     def smooth_cost(self, c, num_steps, dt, batch=1) -> np.ndarray:
         """``(batch, 2)``: R_x = dt sum_l w_l c_l^T Ad c_l and R_t = 1/dt sum_l (c_{l+1} - c_l)^T M (c_{l+1} - c_l) per

@@ -1307,6 +1307,13 @@ class LimitedMemory:
     def drop(self):
         self._ring = []
 
+    def _gram(self, fields, mask=None):
+        """the Gram matrix of ``fields`` in the memory's inner product (here L2(Q))"""
+        return self.ctx.q_gram(fields, self.num_steps, self.dt, mask=mask)
+
+    def _free_set(self, c, g, c_lower, c_upper):
+        self.ctx.free_set(c, g, c_lower, c_upper, self.tl, self._mask)
+
     def push(self, c, c_old, g, g_old) -> bool:
         """Forms s = c - c_old, y = g - g_old and stores the pair if it passes the curvature test."""
         if not self.memory:
@@ -1315,7 +1322,7 @@ class LimitedMemory:
         s, y = self._slots[spare]
         self.ctx.axpby(self.tl, 1.0, c, -1.0, c_old, s)
         self.ctx.axpby(self.tl, 1.0, g, -1.0, g_old, y)
-        G = self.ctx.q_gram([s, y], self.num_steps, self.dt)
+        G = self._gram([s, y])
         if not G[0, 1] > self.PAIR_TOL * np.sqrt(G[0, 0] * G[1, 1]):
             return False
         self._ring.append(spare)
@@ -1328,9 +1335,9 @@ class LimitedMemory:
         (out = -g).  If the quasi-Newton direction is not a descent direction on the free set the ring is dropped and
         out = -g.  ``free_fraction`` is then the share of free values."""
         ctx, tl, k = self.ctx, self.tl, len(self._ring)
-        ctx.free_set(c, g, c_lower, c_upper, tl, self._mask)
+        self._free_set(c, g, c_lower, c_upper)
         F = [self._slots[i][0] for i in self._ring] + [self._slots[i][1] for i in self._ring] + [g]
-        G = ctx.q_gram(F, self.num_steps, self.dt, mask=self._mask)
+        G = self._gram(F, mask=self._mask)
         r, took = two_loop_coefficients(G, k)
         m = np.empty(tl, dtype=np.uint8)
         _lib.check(ctx.handle, _lib.lib.femfct_memcpy_d2h(ctx.handle, m.ctypes.data, dptr(self._mask), tl))
@@ -1348,6 +1355,30 @@ class LimitedMemory:
             y.free()
         self._slots, self._ring = [], []
         self._mask.free()
+
+
+class OmegaLimitedMemory(LimitedMemory):
+    """:class:`LimitedMemory` for one-level fields of n values in the inner product a^T M b of ``l2_norm_sq_Omega`` (the
+    initial state of :func:`initial_state_solidbody`): the Gram matrices come from ``Context.omega_gram`` (L2(Q)'s
+    trapezoid weights are not defined for one level), the two-loop recursion and the combination are unchanged.  A caller
+    that has filled :attr:`mask` for the (v, g) it is about to pass (``Context.initial_gradient`` writes it with g) sets
+    ``mask_ready``; :meth:`direction` then launches no free-set kernel."""
+
+    def __init__(self, ctx: Context, memory: int):
+        super().__init__(ctx, ctx.n, memory, 1.0)
+        self.mask_ready = False
+
+    @property
+    def mask(self):
+        return self._mask
+
+    def _gram(self, fields, mask=None):
+        return self.ctx.omega_gram(fields, mask=mask)
+
+    def _free_set(self, c, g, c_lower, c_upper):
+        if not self.mask_ready:
+            super()._free_set(c, g, c_lower, c_upper)
+        self.mask_ready = False
 
 
 def _lbfgs_iterate(ctx, lm, tl, c, g, bufs, J0, gradient, search, take, c_lower, c_upper, max_iters, gam, s0, K, stop):
@@ -1986,6 +2017,144 @@ def ensemble_solidbody(prob: SolidBodyDrift, scenarios: Ensemble, c0, beta, c_lo
             hist[key] = stats.get(key, [])
         hist["scenario_costs0"] = last[0]
         return (cur["u"].download().reshape(S, tl), p.download().reshape(S, tl), c.download(), hist)
+    finally:
+        lm.close()
+        for a in bufs:
+            a.free()
+
+
+# ---------------------------------------------------------------------------------------------- initial-state recovery
+# An extension (no reference call): every loop above recovers a control under a fixed initial condition; this one keeps the
+# control fixed and recovers the initial condition from later observations of the transported field (4D-Var).
+def initial_state_solidbody(prob: SolidBodyDrift, c, uhat, v0, beta0, v_lower, v_upper, iters, background=None, memory=5,
+                            gam=1e-4, s0=1.0, max_armijo=10, tol=None, optim="finaltime", obs=None, speculative=True):
+    """Projected gradient (``memory=0``) or projected L-BFGS descent on the initial state v of the solid-body problem
+    under the fixed control trajectory ``c``,
+
+        J(v) = T(u(v)) + beta0/2 (v - v_b)^T M (v - v_b),      u(v) = the forward sweep from u_0 = v under c,
+
+    T the tracking term of ``optim`` ("finaltime" / "alltime", or "snapshots" with ``obs``; ``uhat`` shaped as for
+    :func:`lbfgs_solidbody`), ``background`` v_b (None: 0), box ``[v_lower, v_upper]``.  It is the iteration of
+    :func:`lbfgs_solidbody` (``_lbfgs_iterate``) on one level of n values with the inner product a^T M b
+    (:class:`OmegaLimitedMemory`) and three callbacks of its own:
+
+        gradient   the adjoint sweep p of u(v) (the drift loops' call for the mode) and g = beta0 (v - v_b) - p_0 with the
+                   free set, one launch: p(T) = uhat - u(T), so -p_0 is the L2(Omega) representative of the tracking
+                   term's gradient and no mass solve is needed.  p is an FCT discretisation of the continuous adjoint:
+                   g is inexact, as every gradient of this project is
+        search     trials v_t = clip(v + s0/2^t dir), the first with J(v_t) - J <= -gam/s_t ||v_t - v||^2_M accepted.
+                   ``speculative``: the ``max_armijo`` trials are one ``initial_trials`` launch into level 0 of a batch,
+                   one batched forward sweep under the shared control, one tracking-cost call and one
+                   ``initial_trial_stats`` read-back, whatever ``max_armijo`` is; else one trial at a time
+        take       the accepted member's trajectory becomes u (a copy, no second sweep)
+
+    ``max_armijo`` may not exceed ``prob.batch`` when ``speculative``.  Argument errors raise ValueError before any launch.
+
+    Returns ``(u, p, v, history)``; history has the keys of lbfgs_solidbody's plus ``tracking`` and ``background``, the two
+    terms of J at every accepted iterate (``tracking0`` / ``background0`` at ``v0``)."""
+    snap = _need_obs(optim, obs)
+    ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
+    K = int(max_armijo)
+    if K < 1:
+        raise ValueError(f"max_armijo = {max_armijo}: must be >= 1")
+    if speculative and K > min(prob.batch, _lib.MAX_MEMBERS):
+        raise ValueError(f"max_armijo = {K}: a speculative search needs a problem of batch >= max_armijo "
+                         f"(prob.batch = {prob.batch}, at most {_lib.MAX_MEMBERS})")
+    beta0 = float(beta0)
+    if not (np.isfinite(beta0) and beta0 >= 0):
+        raise ValueError(f"beta0 = {beta0}: must be finite and >= 0")
+    v_lower, v_upper = float(v_lower), float(v_upper)
+    if not v_lower <= v_upper:
+        raise ValueError(f"v_lower = {v_lower} > v_upper = {v_upper}")
+    c = np.asarray(c, dtype=np.float64).ravel()
+    if c.size != tl:
+        raise ValueError(f"c of {c.size} values, expected {tl}")
+    v0 = np.asarray(v0, dtype=np.float64).ravel()
+    if v0.size != n:
+        raise ValueError(f"v0 of {v0.size} values, expected {n}")
+    if background is not None:
+        background = np.asarray(background, dtype=np.float64).ravel()
+        if background.size != n:
+            raise ValueError(f"background of {background.size} values, expected {n}")
+    uhat = np.asarray(uhat, dtype=np.float64).ravel()
+    hsize = n if optim == "finaltime" else tl
+    if uhat.size != hsize:
+        raise ValueError(f"target of {uhat.size} values, expected {hsize} for optim='{optim}'")
+    if snap:
+        obs.check(Nt, n)
+    B = K if speculative else 1
+    lm = OmegaLimitedMemory(ctx, memory)
+    bufs = []
+
+    def alloc(count, zero=True):
+        a = ctx.zeros(count) if zero else ctx.empty(count)
+        bufs.append(a)
+        return a
+
+    try:
+        u, p, uB = alloc(tl), alloc(tl), alloc(B * tl)
+        cd = alloc(tl, False).upload(c)
+        v = alloc(n, False).upload(v0)
+        g = alloc(n)
+        qn_bufs = (alloc(n, False), alloc(n, False), alloc(n, False))
+        vb = None if background is None else alloc(n, False).upload(background)
+        uh = alloc(hsize, False).upload(uhat)
+        uhB = alloc(B * hsize, False)
+        for k in range(B):
+            uhB.copy_from(uh, hsize, dst_off=k * hsize)
+        # the tracking term of every mode is the snapshot cost: final-time and all-time through their Observations corners
+        ob, target = prob._corner(optim, obs, uhB, B)
+        _, cost_w, window = prob.obs_device(ob)
+        tracking = lambda uu, b: ctx.obs_cost(uu, target, cost_w, Nt, window, batch=b)
+        u.copy_from(v, n)
+        prob.forward(cd, u, batch=1)
+        T0 = float(tracking(u, 1)[0])
+        B0 = (0.5 * beta0) * float(ctx.l2_norm_sq_Omega(v, vb)[0])
+        last, terms = {}, dict(tracking=[], background=[])
+
+        def gradient():
+            prob.adjoint(cd, u, uh, p, optim, batch=1, obs=obs)
+            ctx.initial_gradient(p, v, beta0, g, vb=vb, v_lower=v_lower, v_upper=v_upper, mask=lm.mask)
+            lm.mask_ready = True
+
+        def evaluate(dirv, steps):
+            """(J, dist, T, background term) of the trials v + steps[k] dir, one batched sweep"""
+            b = len(steps)
+            ctx.initial_trials(v, dirv, steps, v_lower, v_upper, uB, Nt)
+            prob.forward(cd, uB, batch=b, c_shared=True)
+            T = tracking(uB, b)
+            st = ctx.initial_trial_stats(uB, v, b, Nt, vb=vb)
+            Bg = (0.5 * beta0) * st[:, 0]
+            return T + Bg, st[:, 1], T, Bg
+
+        def search(dirv, J_k, svals, margins):
+            if speculative:
+                J, dist, T, Bg = evaluate(dirv, svals)
+                t, looked = _first_accepted(J, dist, J_k, svals, gam, margins)
+                if t is None:
+                    return None, None, None, looked
+                last["terms"] = (float(T[t]), float(Bg[t]))
+                return t, float(J[t]), float(dist[t]), looked
+            for k, s in enumerate(svals):
+                J, dist, T, Bg = evaluate(dirv, [s])
+                t, _ = _first_accepted(J, dist, J_k, [s], gam, margins)
+                if t is not None:
+                    last["terms"] = (float(T[0]), float(Bg[0]))
+                    return k, float(J[0]), float(dist[0]), k + 1
+            return None, None, None, len(svals)
+
+        def take(t):
+            off = t * tl if speculative else 0
+            u.copy_from(uB, tl, src_off=off)
+            v.copy_from(uB, n, src_off=off)
+            terms["tracking"].append(last["terms"][0])
+            terms["background"].append(last["terms"][1])
+
+        stop = lambda J, Jt, dist: tol is not None and abs(J - Jt) / abs(J) < tol
+        hist = _lbfgs_iterate(ctx, lm, n, v, g, qn_bufs, T0 + B0, gradient, search, take, v_lower, v_upper, int(iters), gam,
+                              s0, K, stop)
+        hist.update(terms, tracking0=T0, background0=B0)
+        return u.download(), p.download(), v.download(), hist
     finally:
         lm.close()
         for a in bufs:

@@ -497,6 +497,40 @@ int femfct_drift_gradient_rhs_smooth(femfct_ctx* ctx, const double* c_dev, const
                                      double beta, double beta_x, double beta_t, double dt, double* out_dev, int32_t levels,
                                      double bx, double by);
 
+/* Initial-state recovery (solvers.initial_state_solidbody; added after ABI version 5, backward compatible; an extension
+ * without a counterpart in the reference): the control is fixed and the initial state v = u_0 is the unknown,
+ *   J(v) = T(u(v)) + beta0/2 (v - v_b)^T M (v - v_b),    g = beta0 (v - v_b) - p_0,
+ * T the tracking term of femfct_cost_functional (beta = 0) / femfct_obs_cost, p the adjoint sweep of u(v) and g the
+ * L2(Omega) representative of the gradient (p(T) = uhat - u(T): no mass solve).  Every field is one level of n doubles.
+ * An argument error is FEMFCT_ERR_INVALID and leaves the context usable. */
+/* u_traj[k*(num_steps+1)*n + i] = fmin(fmax(v[i] + steps_host[k]*dir[i], v_lower), v_upper) for the members k < K,
+ * 1 <= K <= FEMFCT_MAX_MEMBERS: the trial states written into level 0 of a batch of K trajectories, where the forward
+ * sweep reads them; no other level is touched.  No contraction: bitwise the NumPy expression.  The steps are read before
+ * the call returns.  v_lower > v_upper is an error.  One launch, does not synchronise. */
+int femfct_initial_trials(femfct_ctx* ctx, const double* v_dev, const double* dir_dev, const double* steps_host, int32_t K,
+                          double v_lower, double v_upper, double* u_traj_dev, int32_t num_steps);
+/* out_host[2 k] = ||v_k - v_b||^2_M and out_host[2 k + 1] = ||v_k - v||^2_M for v_k = level 0 of member k < K of the batch
+ * u_traj_dev, each bit for bit femfct_l2_norm_sq_Omega(v_k, v_b) / (v_k, v) (vb_dev NULL: a zero background, that call's
+ * NULL).  One pass over the members, one fold, one read-back; fixed-order sums, no atomics: two calls return the same bits,
+ * and member k's entries depend on member k alone.  Synchronises. */
+int femfct_initial_trial_stats(femfct_ctx* ctx, const double* u_traj_dev, const double* v_dev, const double* vb_dev,
+                               int32_t K, int32_t num_steps, double* out_host);
+/* g[i] = beta0*(v[i] - vb[i]) - p_traj[i] (vb_dev NULL: v[i] - 0.0), reading level 0 of the adjoint trajectory only; no
+ * contraction: bitwise the NumPy expression, and beta0 = 0 gives -p_0.  mask_dev != NULL: the free set of
+ * femfct_free_set(v, g, v_lower, v_upper, n) from the same pass, byte for byte (mask_dev NULL: the bounds are not used).
+ * beta0 negative or non-finite is an error.  One launch, does not synchronise. */
+int femfct_initial_gradient(femfct_ctx* ctx, const double* p_traj_dev, const double* v_dev, const double* vb_dev,
+                            double beta0, double* g_dev, double v_lower, double v_upper, uint8_t* mask_dev);
+/* The L2(Omega) Gram matrix of J one-level fields (fields_host: J device pointers, read before the call returns; the same
+ * pointer may appear twice), 1 <= J <= FEMFCT_MAX_GRAM_FIELDS: G_host[i*J + j] = (chi.f_i)^T M (chi.f_j), chi = mask_dev
+ * (n bytes as femfct_free_set writes them; NULL: all free; a masked-out value is not read).  The one-level sibling of
+ * femfct_q_gram, whose trapezoid weights are not defined for one level.  Entries i <= j are formed as f_i . (M f_j) and
+ * mirrored: exactly symmetric.  Fixed-order sums, no atomics: two calls return the same bits, and without a mask
+ * G[i][i] = femfct_l2_norm_sq_Omega(f_i, NULL) bit for bit.  femfct_q_combine with count = n forms the combination.
+ * Synchronises. */
+int femfct_omega_gram(femfct_ctx* ctx, const double* const* fields_host, int32_t J, const uint8_t* mask_dev,
+                      double* G_host);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
