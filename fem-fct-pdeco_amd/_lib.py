@@ -23,6 +23,7 @@ ABI_VERSION = 5
 MAX_TRIALS = 16          # FEMFCT_MAX_TRIALS: Armijo trials per femfct_linear_trial_costs / femfct_source_trials call
 MAX_MEMBERS = 256        # FEMFCT_MAX_MEMBERS: problems x trials per femfct_trial_controls / femfct_member_costs call
 MAX_GRAM_FIELDS = 17     # FEMFCT_MAX_GRAM_FIELDS: trajectories per femfct_q_gram / femfct_q_combine call (a memory of 8)
+MAX_ZONES = 256          # FEMFCT_MAX_ZONES: control zones per femfct_set_control_zones table
 
 
 class FemFctError(RuntimeError):
@@ -176,6 +177,9 @@ SIGNATURES = {
     "femfct_initial_trial_stats": (C.c_int, [_p, _p, _p, _p, _i, _i, _p]),
     "femfct_initial_gradient": (C.c_int, [_p, _p, _p, _p, _d, _p, _d, _d, _p]),
     "femfct_omega_gram": (C.c_int, [_p, _p, _i, _p, _p]),
+    "femfct_set_control_zones": (C.c_int, [_p, _p, _i]),
+    "femfct_zone_restrict": (C.c_int, [_p, _p, C.c_int64, _i, _p]),
+    "femfct_zone_prolong": (C.c_int, [_p, _p, _p, C.c_int64, _p]),
     "femfct_smooth_cost": (C.c_int, [_p, _p, _i, _d, _p, _i]),
     "femfct_smooth_rhs": (C.c_int, [_p, _p, _d, _d, _i, _d, _p, _i]),
     "femfct_drift_gradient_rhs_smooth": (C.c_int, [_p, _p, _p, _p, _d, _d, _d, _d, _p, _i, _d, _d]),

@@ -235,6 +235,11 @@ struct femfct_ctx {
     int32_t* d_ttab = nullptr;
     size_t ttab_count = 0;
     std::vector<int32_t> h_ttab;
+    // table of the control zones of femfct_zone_restrict / femfct_zone_prolong (kernels_zones.hip): zone offsets [m+1],
+    // first work item of a zone [m+1], first partial of a zone [m+1], zone of a work item [items], node lists [nodes in
+    // zones], label of a node [n]; zn_m = 0: none registered
+    int32_t* d_ztab = nullptr;
+    int32_t zn_m = 0, zn_items = 0, zn_nparts = 0, zn_listed = 0, zn_maxlen = 0;    // (maxlen: nodes of the largest zone)
 };
 
 // error helpers ---------------------------------------------------------------

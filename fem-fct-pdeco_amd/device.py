@@ -552,6 +552,33 @@ class Context:
         self.time_restrict(x, starts, num_steps, scratch, batch)
         self.time_prolong(scratch, starts, num_steps, x, batch)
 
+    # -- controls piecewise constant in space (solvers.ControlZones) -----------------------------
+    def set_control_zones(self, labels, m=None):
+        """Registers the zone table: ``labels`` (n integers in the pattern's row order; -1: no control at the node,
+        0 .. m-1: its zone; ``m`` default max + 1), or None to clear it.  A bad table raises ValueError and the previous
+        one stays in place."""
+        if labels is None:
+            check(self.handle, lib.femfct_set_control_zones(self.handle, None, 0))
+            return
+        lab = np.asarray(labels).reshape(-1)
+        if lab.size != self.n:
+            raise ValueError(f"set_control_zones: {lab.size} labels for n = {self.n} nodes")
+        if not np.all(lab == np.floor(lab)):
+            raise ValueError("set_control_zones: labels must be integers")
+        lab = np.ascontiguousarray(lab, dtype=np.int32)
+        check(self.handle, lib.femfct_set_control_zones(self.handle, _host_ptr(lab),
+                                                        int(lab.max()) + 1 if m is None else int(m)))
+
+    def zone_restrict(self, x, fields, out, apply_mass=False):
+        """out[f*m + j] = sum over the nodes i of zone j of x_f[i] (``apply_mass``: of (M x_f)[i]) for the ``fields`` fields
+        of n doubles in ``x``; ``out``: fields*m doubles.  Fixed-order sums; does not synchronise."""
+        check(self.handle, lib.femfct_zone_restrict(self.handle, dptr(x), int(fields), int(bool(apply_mass)), dptr(out)))
+
+    def zone_prolong(self, s, fields, out, Ginv=None):
+        """out[f*n + i] = (Ginv s_f)[label_i], 0.0 where no control acts; ``s``: fields*m doubles, ``Ginv``: m*m doubles on
+        the device, row-major (None: the identity, s itself is scattered).  Does not synchronise."""
+        check(self.handle, lib.femfct_zone_prolong(self.handle, dptr(s), dptr(Ginv), int(fields), dptr(out)))
+
     # -- limited-memory quasi-Newton primitives (solvers.LimitedMemory) -----------------------
     @staticmethod
     def _fields(fields):

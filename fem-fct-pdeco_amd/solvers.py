@@ -358,6 +358,123 @@ class ControlIntervals:
         return self
 
 
+class ControlZones:
+    """Controls that are piecewise constant in space: ``labels`` holds one integer per mesh node in the problem's DoF
+    order, ``-1`` where no control acts and ``0 .. m-1`` for the node's zone (every zone non-empty, 1 <= m <= 256).
+
+    Passed as ``control_space=`` to a descent loop, the direction of every time level lies in span{chi_j}, chi_j the P1
+    function that is 1 on the nodes of zone j and 0 on all others: it is the steepest-descent direction among these
+    controls in the mass inner product,
+
+        d = chi G^-1 chi^T r      (drift control: r the dual right-hand side -(beta M c + G_l); no mass solve)
+        d = chi G^-1 chi^T M d    (source control: the orthogonal projection P of the primal direction)
+
+    with G = chi^T M chi (m x m, SPD).  d is exactly 0.0 where the label is -1, so the control keeps clip(c0) there, and
+    every node of a zone receives the same stored value: with scalar bounds and a start control that is constant on every
+    zone each iterate clip(c + s d) stays so bit for bit, and the sweeps, costs and trial kernels are the free loop's.
+    The loops return the control as a full trajectory; :meth:`compact` gives its ``(levels, m)`` amplitudes."""
+
+    def __init__(self, labels):
+        lab = np.asarray(labels)
+        if lab.ndim != 1 or lab.size < 1:
+            raise ValueError("labels: one integer per node is needed")
+        if not np.issubdtype(lab.dtype, np.number) or not np.all(lab == np.floor(lab)):
+            raise ValueError("labels must be integers")
+        lab = lab.astype(np.int64)
+        if lab.min() < -1:
+            raise ValueError(f"labels must be -1 (no control) or a zone 0 .. m-1, got {int(lab.min())}")
+        m = int(lab.max()) + 1
+        if not 1 <= m <= _lib.MAX_ZONES:
+            raise ValueError(f"m = {m} zones: must be in 1..{_lib.MAX_ZONES}")
+        sizes = np.bincount(lab[lab >= 0], minlength=m)
+        if np.any(sizes == 0):
+            raise ValueError(f"zone {int(np.argmin(sizes))} is empty: the labels must use every zone 0 .. {m - 1}")
+        self.n, self.m = lab.size, m
+        self.labels = lab.astype(np.int32)
+        self.sizes = sizes
+        self.active = lab >= 0
+        self.first = np.array([int(np.argmax(lab == j)) for j in range(m)])       # first node of every zone
+        for a in (self.labels, self.sizes, self.active, self.first):
+            a.setflags(write=False)
+
+    @classmethod
+    def single(cls, n):
+        """One zone of all ``n`` nodes: a control that depends on time only."""
+        return cls(np.zeros(int(n), dtype=np.int32))
+
+    @classmethod
+    def blocks(cls, mesh: SquareMeshP1, bx, by, margin=0, order=_lib.ORDER_FENICS):
+        """A ``bx`` x ``by`` grid of rectangles over the square (zone ``jy * bx + jx``); the nodes within ``margin`` node
+        rows of the boundary get -1.  The labels are in the DoF order ``order`` of the problem they are meant for."""
+        bx, by, margin, N = int(bx), int(by), int(margin), mesh.N
+        inner = N - 2 * margin
+        if margin < 0 or bx < 1 or by < 1 or max(bx, by) > inner:
+            raise ValueError(f"blocks: {bx} x {by} blocks do not fit the {inner} x {inner} nodes inside margin = {margin}")
+        iy, ix = np.divmod(np.arange(mesh.nodes), N)
+        inside = (ix >= margin) & (ix < N - margin) & (iy >= margin) & (iy < N - margin)
+        lab = np.where(inside, ((iy - margin) * by // inner) * bx + (ix - margin) * bx // inner, -1)
+        if order != _lib.ORDER_VERTEX:
+            dof = np.empty_like(lab)
+            dof[mesh.vertex_to_dof] = lab
+            lab = dof
+        return cls(lab)
+
+    def check(self, n):
+        """Raises ValueError unless the labels are those of a problem of ``n`` nodes."""
+        if self.n != int(n):
+            raise ValueError(f"control zones of {self.n} nodes for a problem of {n}")
+        return self
+
+    def _levels(self, c, n):
+        self.check(n)
+        c = np.asarray(c, dtype=np.float64)
+        if c.size == 0 or c.size % self.n:
+            raise ValueError(f"control of {c.size} values, expected a multiple of n = {self.n}")
+        return c.reshape(-1, self.n)
+
+    def compact(self, c, n):
+        """The amplitudes of a control trajectory, a ``(levels, m)`` array: its value at the first node of every zone."""
+        return np.ascontiguousarray(self._levels(c, n)[:, self.first])
+
+    def expand(self, a, base=None):
+        """The levels * n trajectory with the amplitudes ``a`` (levels, m) on the zones; where no control acts it holds
+        ``base`` (a trajectory, one level or a number; None: 0)."""
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self.m:
+            raise ValueError(f"amplitudes of shape {a.shape}, expected (levels, {self.m})")
+        out = np.zeros((a.shape[0], self.n))
+        if base is not None:
+            b = np.asarray(base, dtype=np.float64)
+            out[:] = b if b.ndim == 0 else b.reshape(-1, self.n)
+        out[:, self.active] = a[:, self.labels[self.active]]
+        return out.ravel()
+
+    def contains(self, c, n):
+        """True when every level of the control trajectory ``c`` is constant on every zone, exactly."""
+        x = self._levels(c, n)
+        return bool(np.array_equal(x[:, self.active], x[:, self.first][:, self.labels[self.active]]))
+
+    def need(self, c, n):
+        """The loops' entry check: the labels fit the problem and the start control ``c`` lies in the subspace."""
+        self.check(n)
+        if not self.contains(c, n):
+            raise ValueError("c0 is not constant on the control zones (control_space): project it first, e.g. "
+                             "control_space.expand(control_space.compact(c0, n), base=c0), which gives every zone the "
+                             "value at its first node and keeps c0 where no control acts")
+        return self
+
+
+def _direction_kw(prob, c0, control_time, control_space):
+    """The entry checks of ``control_time=`` / ``control_space=`` and the keyword arguments they add to the
+    ``descent_direction`` calls of a loop (neither given: none, today's call exactly)."""
+    kw = {}
+    if control_time is not None:
+        kw["control_time"] = control_time.need(c0, prob.n, prob.num_steps)
+    if control_space is not None:
+        kw["control_space"] = control_space.need(c0, prob.n)
+    return kw
+
+
 class SolidBodyDrift:
     """Drift-control advection problem on one GPU; ``batch`` independent trajectories advance
     together in every kernel launch (Armijo trial steps, regularisation sweeps)."""
@@ -413,6 +530,44 @@ class SolidBodyDrift:
             cache[id(bounds._fields)] = hit
         return hit[1:]
 
+    def zones_device(self, zones: ControlZones):
+        """``Ginv`` of ``zones`` on the device, with the zone table registered on the context.  Once per ControlZones
+        object: G = chi^T M chi is formed on the device as the mass restriction of the m indicator fields, symmetrised
+        and inverted on the host in float64, and uploaded; another ControlZones on the same context registers its table
+        again."""
+        cache = self.__dict__.setdefault("_zones_cache", {})
+        hit = cache.get(id(zones))
+        if hit is None or hit[0] is not zones or self.__dict__.get("_zones_current") is not zones:
+            zones.check(self.n)
+            self.ctx.set_control_zones(zones.labels, zones.m)
+            self.__dict__["_zones_current"] = zones
+        if hit is None or hit[0] is not zones:
+            m = zones.m
+            chi = np.zeros((m, self.n))
+            chi[zones.labels[zones.active], np.flatnonzero(zones.active)] = 1.0
+            x, g = self.ctx.array(chi), self.ctx.empty(m * m)
+            try:
+                self.ctx.zone_restrict(x, m, g, apply_mass=True)
+                G = g.download().reshape(m, m)
+            finally:
+                x.free()
+                g.free()
+            G = 0.5 * (G + G.T)
+            hit = (zones, self.ctx.array(np.linalg.inv(G)), G)
+            cache[id(zones)] = hit
+        return hit[1]
+
+    def _zone_direction(self, zones, x, fields, out, apply_mass):
+        """out = chi G^-1 chi^T (M) x for ``fields`` one-level fields (``out`` may be ``x``): two to three launches"""
+        Ginv = self.zones_device(zones)
+        buf = self.__dict__.get("_zone_buf")
+        if buf is None or buf.count < fields * zones.m:
+            if buf is not None:
+                buf.free()
+            buf = self.__dict__["_zone_buf"] = self.ctx.empty(fields * zones.m)
+        self.ctx.zone_restrict(x, fields, buf, apply_mass=apply_mass)
+        self.ctx.zone_prolong(buf, fields, out, Ginv=Ginv)
+
     def _corner(self, optim, obs, uhat, batch):
         """The observations and the target trajectory of a mode, for the sweeps with state bounds (which are snapshot
         sweeps): final-time and all-time are their :class:`Observations` corners, the final-time target copied to level
@@ -465,13 +620,16 @@ class SolidBodyDrift:
         self.ctx.solidbody_adjoint(self.Arot, c, u, uhat, p, self.num_steps, self.dt, self.eps, self.rot_scale,
                                    self.drift, optim == "alltime", self.batch if batch is None else batch, c_shared)
 
-    def descent_direction(self, c, u, p, beta, d, scratch=None, control_time=None, smoothness=None):
+    def descent_direction(self, c, u, p, beta, d, scratch=None, control_time=None, smoothness=None, control_space=None):
         """d_k = ChebSI(-(beta*M*c_k + int p_k (b.grad u_k) v)) for every level k (finaltime.py:228-238);
         all levels are one batched launch sequence.  ``control_time`` (a :class:`ControlIntervals`): the direction
         projected onto the controls constant on its K intervals.  The projection commutes with the per-level mass solve,
         so the right-hand sides are restricted first and K systems are solved in place of num_steps + 1.
         ``smoothness`` (a :class:`Smoothness`): the right-hand side gains -(beta_x Ad c_k + beta_t M tau_k) in the same
-        launch; the restriction acts on the right-hand side, so it composes with ``control_time`` unchanged."""
+        launch; the restriction acts on the right-hand side, so it composes with ``control_time`` unchanged.
+        ``control_space`` (a :class:`ControlZones`): d_k = chi G^-1 chi^T rhs_k, the steepest-descent direction among the
+        zone-constant controls; the right-hand side is a dual vector, so no mass solve runs at all.  With
+        ``control_time``: time restriction, the zone direction of the K fields, time prolongation."""
         levels = self.num_steps + 1
         own = scratch is None
         rhs = self.ctx.empty(self.tlen) if own else scratch
@@ -481,13 +639,27 @@ class SolidBodyDrift:
             else:
                 self.ctx.drift_gradient_rhs_smooth(c, u, p, beta, smoothness.beta_x, smoothness.beta_t, self.dt, rhs,
                                                    levels, self.drift)
-            if control_time is None:
+            if control_space is not None:
+                self._zone_solve(control_space, control_time, rhs, d, False)
+            elif control_time is None:
                 self.ctx.chebsi(rhs, d, 20, 0.5, 2.0, batch=levels)
             else:
                 self._projected_solve(control_time, rhs, d, 1)
         finally:
             if own:
                 rhs.free()
+
+    def _zone_solve(self, zones, ct, x, d, apply_mass):
+        """d = chi G^-1 chi^T (M) x level by level (``d`` may be ``x``); with the intervals ``ct``: time restriction, the
+        zone operation on the K fields, time prolongation."""
+        if ct is None:
+            self._zone_direction(zones, x, self.num_steps + 1, d, apply_mass)
+            return
+        K = ct.check(self.num_steps).K
+        rk = self._interval_fields(2 * K * self.n)[0]
+        self.ctx.time_restrict(x, ct.starts, self.num_steps, rk, 1)
+        self._zone_direction(zones, rk, K, rk, apply_mass)
+        self.ctx.time_prolong(rk, ct.starts, self.num_steps, d, 1)
 
     def _projected_solve(self, ct, rhs, d, batch):
         """d[b] = prolong(ChebSI(restrict(rhs[b]))) for ``batch`` trajectories: batch * K mass solves in one sequence."""
@@ -587,11 +759,13 @@ class LinearSourceControl(SolidBodyDrift):
         """:259-274 (all-time) / advection_FCT_PDECO_finaltime.py (final-time)"""
         self.adjoint(self._zero_c, u, uhat, p, optim, batch=batch, c_shared=True, obs=obs, state_bounds=state_bounds)
 
-    def descent_direction(self, c, p, beta, d, control_time=None, smoothness=None):
+    def descent_direction(self, c, p, beta, d, control_time=None, smoothness=None, control_space=None):
         """advection_FCT_PDECO_alltime_exact.py:278: d = -(beta*c - p), every level, the script's operation order.
         ``control_time`` (a :class:`ControlIntervals`): then projected onto the controls constant on its intervals.
         ``smoothness`` (a :class:`Smoothness` with a non-zero coefficient): d = -(beta*c - p) + ChebSI(smooth_rhs), one
-        mass solve per level for the term's gradient, before the projection."""
+        mass solve per level for the term's gradient, before the projection.
+        ``control_space`` (a :class:`ControlZones`): then d_k <- chi G^-1 chi^T M d_k, the orthogonal projection in the
+        mass inner product onto the zone-constant controls (with ``control_time``: on its K fields)."""
         if smoothness is not None and smoothness.active:
             buf = self.__dict__.get("_smooth_buf")
             if buf is None:
@@ -603,7 +777,9 @@ class LinearSourceControl(SolidBodyDrift):
             self.ctx.axpby(self.tlen, 1.0, rhs, 1.0, sm, d)
         else:
             self.ctx.descent_pointwise(self.tlen, beta, c, p, d)
-        if control_time is not None:
+        if control_space is not None:
+            self._zone_solve(control_space, control_time, d, d, True)
+        elif control_time is not None:
             K = control_time.check(self.num_steps).K
             self.ctx.time_project(d, control_time.starts, self.num_steps, self._interval_fields(2 * K * self.n)[0])
 
@@ -762,34 +938,36 @@ def _record_smooth(prob, hist, member):
 
 def pgd_solidbody_finaltime(prob: SolidBodyDrift, u0, uhat_T, c0, beta, c_lower, c_upper, iters,
                             gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
-                            state_bounds=None, smoothness=None):
+                            state_bounds=None, smoothness=None, control_space=None):
     """Final-time variant of :func:`pgd_solidbody` (advection_solidbody_FCT_PDECO_finaltime_Garvie.py)."""
     return pgd_solidbody(prob, u0, uhat_T, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="finaltime", control_time=control_time, state_bounds=state_bounds, smoothness=smoothness)
+                         optim="finaltime", control_time=control_time, state_bounds=state_bounds, smoothness=smoothness,
+                         control_space=control_space)
 
 
 def pgd_solidbody_alltime(prob: SolidBodyDrift, u0, uhat_all, c0, beta, c_lower, c_upper, iters,
                           gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
-                          state_bounds=None, smoothness=None):
+                          state_bounds=None, smoothness=None, control_space=None):
     """All-time variant (advection_solidbody_FCT_PDECO_alltime_Garvie.py, config C5's loop): ``uhat_all``
     is the target trajectory ((Nt+1)*n, level 0 = u0)."""
     return pgd_solidbody(prob, u0, uhat_all, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
-                         optim="alltime", control_time=control_time, state_bounds=state_bounds, smoothness=smoothness)
+                         optim="alltime", control_time=control_time, state_bounds=state_bounds, smoothness=smoothness,
+                         control_space=control_space)
 
 
 def pgd_solidbody_snapshots(prob: SolidBodyDrift, u0, uhat, obs: Observations, c0, beta, c_lower, c_upper, iters,
                             gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, control_time=None,
-                            state_bounds=None, smoothness=None):
+                            state_bounds=None, smoothness=None, control_space=None):
     """Snapshot variant of :func:`pgd_solidbody`: ``uhat`` is a (num_steps+1)*n trajectory of which only the levels that
     ``obs`` observes are read (the others may hold anything, NaN included)."""
     return pgd_solidbody(prob, u0, uhat, c0, beta, c_lower, c_upper, iters, gam, s0, max_armijo, speculative, tol,
                          optim="snapshots", obs=obs, control_time=control_time, state_bounds=state_bounds,
-                         smoothness=smoothness)
+                         smoothness=smoothness, control_space=control_space)
 
 
 def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters,
                   gam=1e-4, s0=1.0, max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None,
-                  control_time=None, state_bounds=None, smoothness=None):
+                  control_time=None, state_bounds=None, smoothness=None, control_space=None):
     """Projected gradient descent for the drift-control problem, following the loop of
     advection_solidbody_FCT_PDECO_finaltime_Garvie.py:164-330 / ..._alltime_Garvie.py:164-340 step for step:
 
@@ -808,6 +986,8 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     :class:`Observations`; u is seeded with the target at the observed levels (both modes above, seen as observations).
     ``control_time`` (a :class:`ControlIntervals`): the control is constant in time on its intervals; d is projected onto
     these controls and ``c0`` must be one of them (ValueError otherwise).  None: the free space-time control.
+    ``control_space`` (a :class:`ControlZones`): the control is constant in space on its zones and untouched where no
+    zone lies; d is the steepest-descent direction among these controls and ``c0`` must be one of them.
     ``state_bounds`` (a :class:`StateBounds`): the loop descends J + P, and the history gains ``penalty``,
     ``max_violation`` and ``violated_fraction`` of the accepted iterate, from the pass that costs the trials.
     ``smoothness`` (a :class:`Smoothness`): the loop descends J + R (+ P), the direction's right-hand side gains the
@@ -819,8 +999,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     smk = _smooth_kw(smoothness)
     alltime = optim == "alltime" or snap         # (the target is a trajectory)
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
-    if control_time is not None:
-        control_time.need(c0, n, Nt)
+    dkw = _direction_kw(prob, c0, control_time, control_space)
     B = int(max_armijo) if speculative else 1
     u = ctx.zeros(tl)
     u.upload(np.concatenate([np.asarray(u0, dtype=np.float64), np.zeros(tl - n)]))
@@ -851,10 +1030,7 @@ def pgd_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, it
     try:
         for it in range(iters):
             prob.adjoint(c_prev, u, uh, p, optim, batch=1, obs=obs, **sbk)
-            if control_time is None:
-                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, **smk)
-            else:
-                prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, control_time=control_time, **smk)
+            prob.descent_direction(c_prev, u, p, beta, d, scratch=rhs, **dkw, **smk)
             ctx.project_control(c_prev, s0, d, c_lower, c_upper, c, tl)
             prob.forward(c, u, batch=1)
             J_k = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs, **sbk, **smk)[0])
@@ -1078,7 +1254,7 @@ def pgd_solidbody_lockstep(prob: SolidBodyDrift, u0, uhat, c0, betas, c_lower, c
 
 def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
                        increment="linear", gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
-                       control_time=None, state_bounds=None, smoothness=None):
+                       control_time=None, state_bounds=None, smoothness=None, control_space=None):
     """Projected gradient descent for the linear source-control problem, the loop of
     advection_FCT_PDECO_alltime_exact.py:212-330 (optim="alltime", stop="both") and advection_FCT_PDECO_finaltime.py:
     170-280 (optim="finaltime", stop="cost"):
@@ -1098,6 +1274,8 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
     a trajectory read at the observed levels only.
     ``control_time`` (a :class:`ControlIntervals`): the control is constant in time on its intervals; d is projected onto
     these controls (both increments: in linear mode the sensitivity is S(P d)) and ``c0`` must be one of them.
+    ``control_space`` (a :class:`ControlZones`): the control is constant in space on its zones; d is projected onto these
+    controls in the mass inner product (both increments) and ``c0`` must be one of them.
     ``uhat``: target trajectory (all-time) or uhat_T (final-time, n values); ``g``: fixed source trajectory or None.
     Everything stays in HBM; the host sees scalars only.  Returns ``(u, p, c, hist)`` like the scripts: u and p are the
     last iteration's state and adjoint (at the control that iteration started from), c the last accepted control.
@@ -1141,8 +1319,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
     u0 = np.asarray(u0, dtype=np.float64).ravel()
     if u0.size != n:
         raise ValueError(f"u0 of {u0.size} values, expected {n}")
-    if control_time is not None:
-        control_time.need(c0, n, Nt)
+    dkw = _direction_kw(prob, c0, control_time, control_space)
     bufs = []
 
     def alloc(count, zero=True):
@@ -1179,10 +1356,7 @@ def pgd_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c
                 prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs, **sbk)
             else:
                 prob.adjoint_state(u, uh, p, optim, batch=1)
-            if control_time is None:
-                prob.descent_direction(c, p, beta, d, **smk)
-            else:
-                prob.descent_direction(c, p, beta, d, control_time=control_time, **smk)
+            prob.descent_direction(c, p, beta, d, **dkw, **smk)
             if linear:
                 prob.sensitivity(d, w)
                 J, dist = ctx.linear_trial_costs(u, w, uh, c, d, s0, K, c_lower, c_upper, beta, Nt, dt, optim)
@@ -1438,7 +1612,7 @@ def _first_accepted(J, dist, J_k, svals, gam, margins):
 
 def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, iters, memory=5, gam=1e-4, s0=1.0,
                     max_armijo=10, speculative=True, tol=None, optim="finaltime", obs=None, control_time=None,
-                    state_bounds=None, smoothness=None):
+                    state_bounds=None, smoothness=None, control_space=None):
     """Projected L-BFGS descent for the drift-control problem: the sweeps, cost, direction kernels and Armijo test of
     :func:`pgd_solidbody` with the direction of a :class:`LimitedMemory` of ``memory`` pairs.  Per iteration, at the
     control c with u = S(c) and J = J(u, c):
@@ -1452,8 +1626,8 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
     loop, not a restatement of a script), so an accepted cost never exceeds the previous one.  ``memory=0`` is plain
     projected gradient with this search.  ``speculative=True`` evaluates the ``max_armijo`` trials as one batch, as
     pgd_solidbody does.  With ``control_time`` s, y, g and the free set are constant on every interval, so the iterates
-    stay piecewise constant bit for bit.  ``optim``, ``obs``, ``tol``, ``state_bounds``, ``smoothness``: as in
-    pgd_solidbody.
+    stay piecewise constant bit for bit; with ``control_space`` they are constant on every zone and zero where no zone
+    lies, likewise.  ``optim``, ``obs``, ``tol``, ``state_bounds``, ``smoothness``: as in pgd_solidbody.
 
     Returns ``(u, p, c, history)``; history: ``cost``, ``armijo_k``, ``armijo_margin`` (every trial looked at, the
     quasi-Newton ones first), ``used`` ("qn" / "g"), ``pairs``, ``free_fraction``, ``sweeps`` (state and adjoint sweeps so
@@ -1475,8 +1649,7 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
     uhat = np.asarray(uhat, dtype=np.float64).ravel()
     if uhat.size != (tl if alltime else n):
         raise ValueError(f"target of {uhat.size} values, expected {tl if alltime else n} for optim='{optim}'")
-    if control_time is not None:
-        control_time.need(c0, n, Nt)
+    dkw = _direction_kw(prob, c0, control_time, control_space)
     B = K if speculative else 1
     lm = LimitedMemory(ctx, tl, memory, dt)
     bufs = []
@@ -1505,10 +1678,7 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
 
         def gradient():
             prob.adjoint(c, u, uh, p, optim, batch=1, obs=obs, **sbk)
-            if control_time is None:
-                prob.descent_direction(c, u, p, beta, d, scratch=rhs, **smk)
-            else:
-                prob.descent_direction(c, u, p, beta, d, scratch=rhs, control_time=control_time, **smk)
+            prob.descent_direction(c, u, p, beta, d, scratch=rhs, **dkw, **smk)
             ctx.axpby(tl, -1.0, d, 0.0, None, g)
 
         def search(dirv, J_k, svals, margins):
@@ -1553,7 +1723,7 @@ def lbfgs_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, c_lower, c_upper, 
 
 def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower, c_upper, g=None, optim="alltime",
                          memory=5, gam=1e-4, s0=1.0, max_armijo=10, tol=1e-4, max_iters=1000, stop="both", obs=None,
-                         control_time=None, state_bounds=None, smoothness=None):
+                         control_time=None, state_bounds=None, smoothness=None, control_space=None):
     """Projected L-BFGS descent for the linear source-control problem (:class:`LinearSourceControl`,
     :class:`LinearReactionSourceControl`): the iteration of :func:`lbfgs_solidbody` with the gradient
     -descent_direction = beta c - p, the trial controls and sources of ``femfct_source_trials`` and the ``max_armijo``
@@ -1561,7 +1731,7 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
     compares with the cost of the current iterate, J(S(g + c_k), c_k) (no unconditional first step and no 10 J start
     value).  The loop runs while stop_crit2 = |J_k - J_acc| / |J_k| >= tol, or (stop="both")
     stop_crit = ||c_{k+1} - c_k||^2_Q / ||c_k||^2_Q >= tol, and fewer than ``max_iters`` iterations have run.
-    Arguments (``smoothness`` included) and return value as pgd_source_control; the history is lbfgs_solidbody's with
+    Arguments (``smoothness`` and ``control_space`` included) and return value as pgd_source_control; the history is lbfgs_solidbody's with
     ``stop_crit``, ``stop_crit2``."""
     snap = _need_obs(optim, obs)
     sbk = _bounds_kw(prob, state_bounds)
@@ -1584,8 +1754,7 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
     u0 = np.asarray(u0, dtype=np.float64).ravel()
     if u0.size != n:
         raise ValueError(f"u0 of {u0.size} values, expected {n}")
-    if control_time is not None:
-        control_time.need(c0, n, Nt)
+    dkw = _direction_kw(prob, c0, control_time, control_space)
     lm = LimitedMemory(ctx, tl, memory, dt)
     bufs = []
 
@@ -1617,10 +1786,7 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
                 prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs, **sbk)
             else:
                 prob.adjoint_state(u, uh, p, optim, batch=1)
-            if control_time is None:
-                prob.descent_direction(c, p, beta, d, **smk)
-            else:
-                prob.descent_direction(c, p, beta, d, control_time=control_time, **smk)
+            prob.descent_direction(c, p, beta, d, **dkw, **smk)
             ctx.axpby(tl, -1.0, d, 0.0, None, gr)
 
         def search(dirv, J_k, svals, margins):

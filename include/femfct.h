@@ -531,6 +531,29 @@ int femfct_initial_gradient(femfct_ctx* ctx, const double* p_traj_dev, const dou
 int femfct_omega_gram(femfct_ctx* ctx, const double* const* fields_host, int32_t J, const uint8_t* mask_dev,
                       double* G_host);
 
+/* Control zones: controls that are piecewise constant in space on sets of nodes (solvers.ControlZones; an extension, no
+ * reference call).  labels_host: n values in the pattern's row order, -1 = no control acts at the node, 0 .. m-1 = its
+ * zone; every zone is non-empty and 1 <= m <= FEMFCT_MAX_ZONES.  With chi_j the nodal indicator of zone j,
+ *   restrict:  out_dev[f*m + j] = sum_{i in zone j} y_i,   y = x_f (apply_mass = 0) or y = M x_f (apply_mass = 1): chi^T (M) x
+ *   prolong:   out_dev[f*n + i] = delta_f[label_i] (0.0 where label_i = -1),   delta_f = Ginv s_f (Ginv_dev NULL: s_f)
+ * for the `fields` one-level fields of n values that lie back to back in x_dev / out_dev.  With G = chi^T M chi (the
+ * restriction with apply_mass = 1 of the m indicator fields) and Ginv its inverse, prolong(restrict(x, 1)) is the
+ * orthogonal projection in the mass inner product onto span{chi_j}, and prolong(restrict(r, 0)) the steepest-descent
+ * direction among zone-constant controls for a dual right-hand side r.
+ * femfct_set_control_zones registers the table (after the pattern; a new pattern drops it): a label outside -1 .. m-1, an
+ * empty zone or m out of range is FEMFCT_ERR_INVALID and the previous table stays in place; labels_host NULL clears (m is
+ * ignored).  It is the only call that reads labels_host, and it synchronises.
+ * A row of M x is formed as the quadratic forms form it (diagonal slot, then slots 1 .. W-1); a zone's sum runs over its
+ * node list (ascending) in chunks of a fixed size, chunk sums folded in order: the order depends on the zone table alone
+ * (no atomics), the same bits for every `fields`, every position of a field and every run.  delta_f[j] =
+ * ((Ginv[j][0] s[0] + Ginv[j][1] s[1]) + ...) in index order without contraction, Ginv_dev m x m row-major; all nodes of a
+ * zone receive the same stored value.  The out_dev of a prolong may be the x_dev its restrict read.  At most two launches
+ * per call, neither synchronises; without a registered table both are FEMFCT_ERR_INVALID. */
+#define FEMFCT_MAX_ZONES 256
+int femfct_set_control_zones(femfct_ctx* ctx, const int32_t* labels_host, int32_t m);
+int femfct_zone_restrict(femfct_ctx* ctx, const double* x_dev, int64_t fields, int32_t apply_mass, double* out_dev);
+int femfct_zone_prolong(femfct_ctx* ctx, const double* s_dev, const double* Ginv_dev, int64_t fields, double* out_dev);
+
 /* descent direction of the pointwise-gradient problems, d = -(beta*c - t) with t = x*y/divisor (y given)
  * or t = scale*x (y NULL): nonlinear_FCT_PDECO_refactored.py:148, Schnak_FCT_PDECO_refactored.py:167,
  * chemotaxis_FCT_PDECO_AT_refactored.py:158 (same floating-point operation order) */
