@@ -12,6 +12,9 @@
 #include "../../include/femfct.h"
 
 #define FEMFCT_MAX_W 16          // widest ELL row supported (P1 structured mesh: 7)
+// bits of FEMFCT_TILE_TRIM (femfct_ctx::tile_trim)
+enum { TILE_TRIM_WAVES = 1, TILE_TRIM_WT = 8 };      // (2 and 4 were built, measured slower and removed: DESIGN 8.3)
+#define TILE_TRIM_DEFAULT (TILE_TRIM_WAVES | TILE_TRIM_WT)
 #ifndef FEMFCT_MAX_PARTIALS
 #define FEMFCT_MAX_PARTIALS 2048 // cap on per-kernel block partials (row chunks beyond)
 #endif
@@ -143,6 +146,13 @@ struct femfct_ctx {
     int tile_lean = 1;          // 32-patch sweep loops: own value in a register, static LDS buffers, live nodes only (FEMFCT_TILE_LEAN)
     int tile_cone = 0;          // lean loops: liveness and loads by the hexagonal dependency cone of the P1 stencil (FEMFCT_TILE_CONE; needs tile_lean; off: measured no faster)
     int tile_fit = 1;           // fused du/dt and limiter launches: 6 x 6 tiles on 26 / 30 patches while every workgroup gets a CU (FEMFCT_TILE_FIT; needs tile_lean)
+    // prologues and epilogues of the four latency-regime launches (FEMFCT_TILE_TRIM, a bit mask; needs the lean loops without
+    // the cone; 0: the kernels as they were).  TILE_TRIM_WAVES: the Jacobi launches of a deferred-test solve end with their
+    // owning waves.  TILE_TRIM_WT: write-through output stores.
+    int tile_trim = TILE_TRIM_DEFAULT;
+    // what the launchers made of it (femfct_tile_trim_info): whether a launch was enqueued with the owning-wave epilogue /
+    // with write-through stores, partial slots per array of the last deferred-test solve
+    int32_t trim_seen[3] = {0, 0, 0};
     bool exact_iters = false;   // last fused launch logs per-sweep residuals (exact sweep count; measured 10 % slower)
     int32_t bandwidth = 0;      // max |col - row| of the pattern
     int32_t strip_k = 0;        // 0: automatic
@@ -310,6 +320,8 @@ int femfct_enqueue_strip_cheb(femfct_ctx* ctx, const StripPlan& pl, const double
 
 // -- kernels_tile32.hip: 32 x 32 tiles of the structured mesh, latency regime
 struct TilePlan { int tiles, K, H; };
+int femfct_tile_trim_mask(const femfct_ctx* ctx);                        // the bits of FEMFCT_TILE_TRIM that select kernels in this context
+int femfct_tile_wave_slots(const femfct_ctx* ctx, const TilePlan& pl);   // TILE_TRIM_WAVES: partial slots per array (0: per workgroup)
 bool femfct_tile_plan(const femfct_ctx* ctx, TilePlan* pl, bool need_partials = true, int budget = 0, int batch = 1);
 bool femfct_tile_big(const femfct_ctx* ctx, const TilePlan& pl);   // more workgroups than in-kernel partials
 bool femfct_cheb_flux_fusable(const femfct_ctx* ctx, int32_t batch);
@@ -320,16 +332,18 @@ void femfct_tile_phase_dump(const char* path);   // phase stamps of the tile ker
 bool femfct_geom_mass(const femfct_ctx* ctx);   // M may be derived from the cell geometry instead of loaded
 int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, struct MatRef A, const double* Nm, int32_t nshared,
                                      struct VecRef rhs, int64_t rhs_bstride, struct VecRef u_n, int64_t u_bstride, double dt,
-                                     int32_t batch, bool pre = false);
+                                     int32_t batch, bool pre = false, bool wave_slots = false);
 int femfct_enqueue_low_seq(femfct_ctx* ctx, const double* A, double* L, double* D, int32_t entries, double dt);
 int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double* L, const double* b, double* xa,
-                               double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch = 0, int defer = 0);
+                               double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch = 0, int defer = 0,
+                               bool wave_slots = false);
 // k_reduce_resid behind a launch that left `count` residual partials per batch member in d_bigpart (both 2-D families;
 // internal to the library: not exported)
 __attribute__((visibility("hidden"))) void femfct_launch_reduce_resid(femfct_ctx* ctx, int64_t count, int launch, int32_t batch);
 int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, struct MatRef A, struct VecRef rhs, int64_t rhs_bstride, double* ulow,
                                   int budget_units, int part_count, int iters_per_unit, int exact_k, int iters,
-                                  const double* omegas, double md_scale, int32_t batch, int* tail_first = nullptr);
+                                  const double* omegas, double md_scale, int32_t batch, int* tail_first = nullptr,
+                                  bool wave_slots = false);
 int femfct_enqueue_tile_cheb(femfct_ctx* ctx, const TilePlan& pl, const double* b, const double* in_mid,
                              const double* in_old, double* y_out, int k_first, int k_last, const double* omegas,
                              double md_scale, double* bufA0, double* bufA1, double* bufB0, double* bufB1, int32_t batch,

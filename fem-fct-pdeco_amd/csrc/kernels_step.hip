@@ -694,6 +694,7 @@ int femfct_enqueue_step_op(femfct_ctx* ctx, MatRef A, const SbOpArgs* sb, const 
     const bool tiles = femfct_tile_plan(ctx, &tp, false, budget, batch) && (!femfct_tile_big(ctx, tp) || ctx->d_bigpart);
     const bool strips = !tiles && femfct_strip_plan(ctx, &pl);
     int units = budget, part_count = 0, ipu = 1, exact_k = 0;
+    bool wave_slots_used = false;   // the Jacobi launches published per owning wave (TILE_TRIM_WAVES): part_count slots
     const bool tile4 = tiles && femfct_tile4_wanted(ctx, batch);
     // latency regime: the operator construction rides in the first tile-Jacobi launch
     const bool fused_build = ctx->fuse_build && tiles && !tile4 && !femfct_tile_big(ctx, tp) &&
@@ -757,15 +758,19 @@ int femfct_enqueue_step_op(femfct_ctx* ctx, MatRef A, const SbOpArgs* sb, const 
         // residual tests move out of the later launches into that kernel (exact_k = -1; solve_ctl.h: deferred_test_*)
         const bool defer = ctx->defer_check && fused_build && units >= 2 && units <= 4 && exact_k == 0 && ctx->fuse_dudt;
         if (defer) exact_k = -units;
+        // trimmed launches (FEMFCT_TILE_TRIM): partials per owning wave where the test is deferred
+        const int wave_slots = defer ? femfct_tile_wave_slots(ctx, tp) : 0;
+        if (defer) ctx->trim_seen[2] = wave_slots;
+        if (wave_slots) { part_count = wave_slots; wave_slots_used = true; }
         if (fused_build) {
             int r = femfct_enqueue_tile_build_jacobi(ctx, tp, pre_low ? L_pre : A, N, nshared, rhs, rhs_bstride, u_n, u_bstride,
-                                                     dt, batch, pre_low);
+                                                     dt, batch, pre_low, wave_slots_used);
             if (r != FEMFCT_OK) return r;
         }
         for (int s = fused_build ? 1 : 0; s < units; ++s)
             femfct_enqueue_tile_jacobi(ctx, tp, ctx->d_L, ctx->d_b, ctx->d_xa, ctx->d_xb, s,
                                        fused_build ? tp.tiles * tp.tiles : (int)g.grid.x, batch,
-                                       exact_k > 0 && s == units - 1, fused_build ? 1 : 0, defer ? 1 : 0);
+                                       exact_k > 0 && s == units - 1, fused_build ? 1 : 0, defer ? 1 : 0, wave_slots_used);
     } else if (strips) {
         units = (budget + pl.K - 1) / pl.K;
         part_count = pl.S;
@@ -785,8 +790,9 @@ int femfct_enqueue_step_op(femfct_ctx* ctx, MatRef A, const SbOpArgs* sb, const 
         cheb_omegas(20, 0.5, 2.0, om);
         int tail = 0;
         const bool fuse_tail = femfct_cheb_flux_fusable(ctx, batch);
-        femfct_enqueue_tile_dudt_cheb(ctx, A, rhs, rhs_bstride, ulow, units, part_count, ipu, exact_k, 20, om.data(), 1.25,
-                                      batch, fuse_tail ? &tail : nullptr);
+        int rd = femfct_enqueue_tile_dudt_cheb(ctx, A, rhs, rhs_bstride, ulow, units, part_count, ipu, exact_k, 20, om.data(), 1.25,
+                                               batch, fuse_tail ? &tail : nullptr, wave_slots_used);
+        if (rd != FEMFCT_OK) return rd;
         if (fuse_tail && tail > 0) {
             // iterations tail..20 of du/dt + flux + limiter (+ step end) in one launch
             const bool fuse_end = ctx->end_req_delta != 0 && ctx->d_ticket && ctx->d_level && ctx->d_log && !ctx->prof_on;

@@ -29,25 +29,39 @@
 
 namespace {
 
-// Phase stamps of the four launches of a latency-regime step (make tuning; FEMFCT_TILE_TRACE=<file>): thread 0 of a
-// workgroup in the middle of the grid reads the 100 MHz clock at entry, once every load of the load phase is back
-// (behind the barrier that publishes the staged iterate) and at the end, and adds the two differences to sums that
-// femfct_tile_phase_dump writes out.  Read the shares, not the lengths.  The product library carries none of it.
+// Phase stamps of the four launches of a latency-regime step (make tuning; FEMFCT_TILE_TRACE=<file>): the first lane of
+// the wave that holds the tile's first owned node (it works through the kernel's last instruction whatever the epilogue
+// does), in a workgroup in the middle of the grid, reads the 100 MHz clock at entry, once every load of the load phase
+// is back (behind the barrier that publishes the staged iterate), behind the barrier of the last sweep or iteration (in
+// the limiter also behind the barrier between fluxes and limiter) and at the end, and adds the differences to sums
+// that femfct_tile_phase_dump writes out.  Read the shares, not the lengths.  The product library carries none of it.
 #ifdef FEMFCT_TUNING
-__device__ unsigned long long g_tile_phase[4][4];        // [kernel][ticks of the load phase, ticks in all, launches, unused]
-#define TILE_STAMP_BEGIN()                                                                                              \
-    unsigned long long ts0_ = 0, ts1_ = 0;                                                                              \
-    const bool ts_on_ = threadIdx.x == 0 && blockIdx.z == 0 && blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.x / 2; \
-    if (ts_on_) ts0_ = __builtin_amdgcn_s_memrealtime()
+__device__ unsigned long long g_tile_phase[4][6];        // [kernel][ticks: load phase, in all, launches, to the last sweep's barrier, to the flux barrier, unused]
+#define TILE_STAMP_BEGIN(thread)                                                                                        \
+    unsigned long long ts0_ = 0, ts1_ = 0, ts3_ = 0, ts4_ = 0;                                                          \
+    const bool ts_on_ = (int)threadIdx.x == (thread) / WAVE * WAVE && blockIdx.z == 0 && blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.x / 2; \
+    if (ts_on_) ts0_ = ts3_ = ts4_ = __builtin_amdgcn_s_memrealtime()
 #define TILE_STAMP_LOADED() do { if (ts_on_) { __builtin_amdgcn_s_waitcnt(0); ts1_ = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#define TILE_STAMP_SWEPT() do { if (ts_on_) ts3_ = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define TILE_STAMP_FLUXES() do { if (ts_on_) ts4_ = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define TILE_STAMP_END(id) do { if (ts_on_) {                                                                           \
         const unsigned long long ts2_ = __builtin_amdgcn_s_memrealtime();                                               \
-        g_tile_phase[id][0] += ts1_ - ts0_; g_tile_phase[id][1] += ts2_ - ts0_; g_tile_phase[id][2] += 1; } } while (0)
+        g_tile_phase[id][0] += ts1_ - ts0_; g_tile_phase[id][1] += ts2_ - ts0_; g_tile_phase[id][2] += 1;               \
+        g_tile_phase[id][3] += ts3_ - ts0_; g_tile_phase[id][4] += ts4_ - ts0_; } } while (0)
 #else
-#define TILE_STAMP_BEGIN() do { } while (0)
+#define TILE_STAMP_BEGIN(thread) do { } while (0)
 #define TILE_STAMP_LOADED() do { } while (0)
+#define TILE_STAMP_SWEPT() do { } while (0)
+#define TILE_STAMP_FLUXES() do { } while (0)
 #define TILE_STAMP_END(id) do { } while (0)
 #endif
+
+// The output stores of the four launches.  TILE_TRIM_WT (FEMFCT_TILE_TRIM bit 8): agent-scope relaxed atomic stores, which
+// are plain write-through stores (sc1) -- no dirty line is left for the write-back at the kernel's end.  The value stored
+// is the same; whoever reads it is a later launch.
+#define TILE_OUT(lvalue, value) do {                                                                                    \
+        if constexpr ((TRIM & 8) != 0) __hip_atomic_store(&(lvalue), (value), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+        else (lvalue) = (value); } while (0)
 
 struct TileGeom {
     int lx, ly, gx, gy, i;
@@ -97,6 +111,17 @@ __device__ __forceinline__ TileGeom tile_geom(int N) {
 template <int PL>
 __device__ __forceinline__ bool tile_spare() {
     return PL * PL % WAVE != 0 && threadIdx.x >= PL * PL;
+}
+
+// The waves of a 32-patch workgroup that hold owned nodes (FEMFCT_TILE_TRIM bit 1): a wave is two patch rows, the owned
+// rows are H .. 31 - H -- four waves of sixteen at H = 12 and 13.  Every other lane carries the identity of the
+// reductions that end the Jacobi launches, so these waves alone have something to publish; a wave of a border tile whose
+// rows lie outside the mesh publishes the identity.
+__host__ __device__ constexpr int tile_owning_waves(int H) { return (TILE_L - 1 - H) / 2 - H / 2 + 1; }
+template <int H>
+__device__ __forceinline__ int tile_owning_wave() {       // 0 .. tile_owning_waves(H) - 1, or -1; uniform over the wave
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x / WAVE) - H / 2;
+    return w < tile_owning_waves(H) ? w : -1;             // (w < 0 is -1 or below already)
 }
 
 // ---- lean sweep loops (LEAN = 1, FEMFCT_TILE_LEAN) ----------------------------------------------------
@@ -205,13 +230,18 @@ __device__ __forceinline__ void lean_cheb_iter(const LeanAddr& a, bool live, con
 
 // BIG = 1: grids with more workgroups than in-kernel partials (bandwidth regime); the residual maxima
 // go through k_reduce_resid.  A template parameter so that profiles list the two regimes separately.
-template <int H, int EXACT, int BIG, int LEAN>
+// TRIM (FEMFCT_TILE_TRIM, lean loops only): bit 1 (deferred-test launches) -- the launch ends with its owning waves
+// (tile_owning_waves: no block reduction, one partk slot per owning wave); bit 8 -- write-through output stores (TILE_OUT).
+// 0 is the kernel as it was.
+template <int H, int EXACT, int BIG, int LEAN, int TRIM = 0>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restrict__ b_, double* __restrict__ xa_,
               double* __restrict__ xb_, double* __restrict__ part, StepCtl* __restrict__ ctl_, int launch, int K,
               int g_build, double rel_tol, double* __restrict__ bigpart, double* __restrict__ partk, int bn_launch,
               int defer) {
     constexpr int W = 7;
+    static_assert(!TRIM || (LEAN == 1 && !BIG), "trimmed launches: lean loops");
+    static_assert(!(TRIM & 1) || !EXACT, "owning-wave epilogue: deferred test");
     __shared__ double xs[2][TILE_L * TILE_LD];
     __shared__ double smem[96];
     const int bz = blockIdx.z;
@@ -270,7 +300,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
     const double* L = L_ + moff;
     const double* xin = ((launch & 1) ? xb_ : xa_) + voff;
     double* xout = ((launch & 1) ? xa_ : xb_) + voff;
-    TILE_STAMP_BEGIN();
+    TILE_STAMP_BEGIN(H * TILE_L + H);
     const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
     constexpr bool CONE = LEAN == 2;
     double lv[W - 1], dg = 1.0, rdg = 1.0, bv = 0.0, xi = 0.0;
@@ -321,6 +351,7 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
             __syncthreads();
             cur ^= 1;
         }
+        TILE_STAMP_SWEPT();
     } else {
         // last launch of the budget, optional: log the residual of every sweep's input so that the
         // host learns the exact sweep count (fully unrolled: per-sweep values stay in registers)
@@ -372,7 +403,18 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
             partk[((int64_t)bz * 16 + threadIdx.x) * FEMFCT_MAX_PARTIALS + wg] = v;
         }
     }
-    if (g.owned) xout[g.i] = LEAN ? xo : xs[cur][g.self];        // LEAN: no LDS read-back
+    if (g.owned) TILE_OUT(xout[g.i], LEAN ? xo : xs[cur][g.self]);        // LEAN: no LDS read-back
+    if constexpr (TRIM & 1) {
+        // deferred test only (the launcher sees to it): one slot of this launch's partk row per owning wave
+        const int ow = tile_owning_wave<H>();
+        if (ow >= 0) {
+            rmax = wave_reduce(rmax, OpMax());
+            if (threadIdx.x % WAVE == 0)
+                partk[((int64_t)bz * 16 + launch) * FEMFCT_MAX_PARTIALS + wg * tile_owning_waves(H) + ow] = rmax;
+        }
+        TILE_STAMP_END(1);
+        return;
+    }
     rmax = block_reduce(rmax, OpMax(), 0.0, smem);
     if (threadIdx.x == 0) {
         if (BIG) bigpart[(int64_t)bz * nwg + wg] = rmax;
@@ -389,7 +431,9 @@ k_tile_jacobi(int n, int N, const double* __restrict__ L_, const double* __restr
 // limiter, then K Jacobi sweeps run as in k_tile_jacobi.  Saves one dependent launch per time step.
 // PRE = 1: the operator was built before the sweep (k_low_seq): A_ref is the L_k sequence, read instead of built (no
 // a_ji exchange, no D store: the limiter reads D_k from the sequence); the owned rows of L still go to L_ for launch 1.
-template <int H, int PRE, int LEAN>
+// TRIM (FEMFCT_TILE_TRIM, lean loops): bit 1 (solves whose test is deferred) -- the three partials per owning wave instead
+// of per workgroup, no block reduction; bit 8 -- write-through output stores (TILE_OUT).  0 is the kernel as it was.
+template <int H, int PRE, int LEAN, int TRIM = 0>
 __global__ void __launch_bounds__(STRIP_T)
 k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, int nshared,
                     VecRef rhs_ref, int64_t rhs_bstride, VecRef u_ref, int64_t u_bstride,
@@ -397,6 +441,7 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
                     double* __restrict__ b_, double* __restrict__ xb_, double* __restrict__ part,
                     StepCtl* __restrict__ ctl_, int K) {
     constexpr int W = 7;
+    static_assert(!TRIM || LEAN == 1, "trimmed launches: lean loops");
     __shared__ double xs[2][TILE_L * TILE_LD];
     __shared__ double as[PRE ? 1 : 3][TILE_L * TILE_LD];
     __shared__ double smem[96];
@@ -414,7 +459,7 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
     const double* rhs = vec_ptr(rhs_ref);
     if (rhs) rhs += bz * rhs_bstride;
     const double* u = vec_ptr(u_ref) + bz * u_bstride;
-    TILE_STAMP_BEGIN();
+    TILE_STAMP_BEGIN(H * TILE_L + H);
     const TileGeom g = tile_geom<TILE_L - 2 * H, H>(N);
     double lv[W - 1], dv[W - 1], dsum = 0.0, rs = 0.0;
     double dg = 1.0, rdg = 1.0, bv = 0.0, xi = 0.0;
@@ -510,16 +555,16 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
     double bmax = 0.0, rsmin = INFINITY;
     if (g.owned) {
         double* L = L_ + moff;
-        L[g.i] = dg;
+        TILE_OUT(L[g.i], dg);
 #pragma unroll
-        for (int s = 1; s < W; ++s) L[(int64_t)s * n + g.i] = lv[s - 1];
+        for (int s = 1; s < W; ++s) TILE_OUT(L[(int64_t)s * n + g.i], lv[s - 1]);
         if constexpr (!PRE) {
             double* D = D_ + moff;
             D[g.i] = -dsum;
 #pragma unroll
             for (int s = 1; s < W; ++s) D[(int64_t)s * n + g.i] = dv[s - 1];
         }
-        b_[voff + g.i] = bv;
+        TILE_OUT(b_[voff + g.i], bv);
         bmax = fabs(bv);
         rsmin = rs;
     }
@@ -546,7 +591,25 @@ k_tile_build_jacobi(int n, int N, MatRef A_ref, const double* __restrict__ N_, i
         __syncthreads();
         cur ^= 1;
     }
-    if (g.owned) xb_[voff + g.i] = LEAN ? xo : xs[cur][g.self];
+    TILE_STAMP_SWEPT();
+    if (g.owned) TILE_OUT(xb_[voff + g.i], LEAN ? xo : xs[cur][g.self]);
+    if constexpr (TRIM & 1) {
+        // deferred test only (the launcher sees to it): deferred_test_load alone reads these, slot by slot
+        const int ow = tile_owning_wave<H>();
+        if (ow >= 0) {
+            rmax = wave_reduce(rmax, OpMax());
+            bmax = wave_reduce(bmax, OpMax());
+            rsmin = wave_reduce(rsmin, OpMin());
+            if (threadIdx.x % WAVE == 0) {
+                const int slot = wg * tile_owning_waves(H) + ow;
+                p[slot] = rmax;
+                p[2 * FEMFCT_MAX_PARTIALS + slot] = bmax;
+                p[3 * FEMFCT_MAX_PARTIALS + slot] = rsmin;
+            }
+        }
+        TILE_STAMP_END(0);
+        return;
+    }
     block_reduce_max_max_min(rmax, bmax, rsmin, smem);
     if (threadIdx.x == 0) {
         p[wg] = rmax;
@@ -804,7 +867,8 @@ k_tile_flux_limit(int n, int N, double h, const double* __restrict__ M, const do
 // PL (FEMFCT_TILE_FIT): the patch edge.  32 is the 8 x 8 tile; 30 is a 6 x 6 tile whose halo of 12 needs no more -- 15
 // waves instead of 16 and more workgroups, chosen while each still gets a compute unit (femfct_tile_fit).  The block is
 // PL^2 threads rounded up to whole waves; the spare threads own no node (tile_geom).
-template <int GEOM, int LEAN, int PL>
+// TRIM (FEMFCT_TILE_TRIM, lean loops): bit 8 -- write-through output store (TILE_OUT).  0 is the kernel as it was.
+template <int GEOM, int LEAN, int PL, int TRIM = 0>
 __global__ void __launch_bounds__((PL * PL + WAVE - 1) / WAVE * WAVE, (LEAN && PL == TILE_L) ? 8 : 1)
 k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, const double* __restrict__ b_,
                        const double* __restrict__ ymid_, const double* __restrict__ yold_, int K, CheOmegas om,
@@ -813,12 +877,13 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
     constexpr int W = 7, HH = 12, PLD = PL + 1;
     constexpr bool CONE = LEAN == 2;
     static_assert(PL == TILE_L || LEAN, "fitted patches run the lean loops only");
+    static_assert(!TRIM || LEAN == 1, "trimmed launches: lean loops");
     __shared__ double ys[LEAN ? 2 : 3][PL * PLD];
     __shared__ double su[PL * PLD], srp[PL * PLD], srm[PL * PLD];
     const int bz = blockIdx.z;
     const int64_t voff = (int64_t)bz * n;
     const double* D_ = mat_ptr(D_ref, bz);     // the step's D (one of the pre-built sequence, or the workspace's)
-    TILE_STAMP_BEGIN();
+    TILE_STAMP_BEGIN(HH * PL + HH);
     const TileGeom g = tile_geom<PL - 2 * HH, HH, PL>(N);
     double mv[W - 1], dv[W - 1], md = 1.0, rmd = 1.0, bv = 0.0, ym = 0.0, yo = 0.0, ui = 0.0, mli = 1.0;
 #pragma unroll
@@ -916,6 +981,7 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         __syncthreads();
         int t = io; io = im; im = in_; in_ = t;
     }
+    TILE_STAMP_SWEPT();
     const double* sd = ys[im];
     const double dui = LEAN ? ym : sd[g.self];
     double f[W - 1];
@@ -938,6 +1004,7 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
         srm[g.self] = (pm != 0.0) ? fmin(1.0, mli * qm / (dt * pm)) : 1.0;
     }
     __syncthreads();
+    TILE_STAMP_FLUXES();
     if (g.owned) {
         const double rpi = srp[g.self], rmi = srm[g.self];
         double fbar = 0.0;
@@ -948,7 +1015,7 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
             fbar += a * fs;
         }
         double* out = const_cast<double*>(vec_ptr(out_ref)) + bz * out_bstride;
-        out[g.i] = ui + dt * fbar / mli;
+        TILE_OUT(out[g.i], ui + dt * fbar / mli);
     }
     TILE_STAMP_END(3);
     step_end_by_last_workgroup(e);
@@ -960,7 +1027,10 @@ k_tile_cheb_flux_limit(int n, int N, double h, const double* __restrict__ M, con
 // Also finalises the low-order solve's bookkeeping (what k_dudt_rhs does in the unfused sequence).
 // GEOM: the off-diagonals of the mesh's own mass matrix from the cell geometry (as k_tile_cheb_flux_limit) instead of
 // six loads per node.  PL (FEMFCT_TILE_FIT): patch edge 32 (12 x 12 tile) or 26 (6 x 6 tile, 11 waves: femfct_tile_fit).
-template <int LEAN, int GEOM, int PL>
+// TRIM (FEMFCT_TILE_TRIM, lean loops): bit 1 -- the Jacobi launches left one partial per owning wave (part_count of them):
+// all waves of the test's workgroup load them (deferred_test_load_wide); bit 8 -- write-through output stores (TILE_OUT).
+// 0 is the kernel as it was.
+template <int LEAN, int GEOM, int PL, int TRIM = 0>
 __global__ void __launch_bounds__((PL * PL + WAVE - 1) / WAVE * WAVE)
 k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t rhs_bstride,
                  const double* __restrict__ M, const double* __restrict__ xa_, const double* __restrict__ xb_,
@@ -971,6 +1041,7 @@ k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t r
     constexpr int W = 7, H = 10, PLD = PL + 1;
     constexpr bool CONE = LEAN == 2;
     static_assert(PL == TILE_L || LEAN, "fitted patches run the lean loops only");
+    static_assert(!TRIM || LEAN == 1, "trimmed launches: lean loops");
     __shared__ double ys[LEAN ? 2 : 3][PL * PLD];
     __shared__ double smem[64];
     const int bz = blockIdx.z;
@@ -980,9 +1051,13 @@ k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t r
     if (exact_k < 0 && blockIdx.y == gridDim.x) {
         // deferred test: the launch carries one extra row of workgroups; its first one does nothing but reduce the solve's
         // partials and write the step record (no tile behind it: no workgroup of the kernel ends later for it)
-        if (blockIdx.x == 0)
-            deferred_test_publish(ctl, deferred_test_load(p, partk + (int64_t)bz * 16 * FEMFCT_MAX_PARTIALS, part_count, -exact_k),
-                                  -exact_k, iters_per_unit, rel_tol);
+        if (blockIdx.x == 0) {
+            const double* pk = partk + (int64_t)bz * 16 * FEMFCT_MAX_PARTIALS;
+            if constexpr (TRIM & 1)
+                deferred_test_publish(ctl, deferred_test_load_wide(p, pk, part_count, -exact_k, &ys[0][0]), -exact_k, iters_per_unit, rel_tol);
+            else
+                deferred_test_publish(ctl, deferred_test_load(p, pk, part_count, -exact_k), -exact_k, iters_per_unit, rel_tol);
+        }
         return;
     }
     // deferred test (exact_k < 0): no launch of the solve set `done`, the iterate is the budget-parity one; nothing below
@@ -997,7 +1072,7 @@ k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t r
     const double* x = (parity ? xb_ : xa_) + voff;
     const double* rhs = vec_ptr(rhs_ref);
     if (rhs) rhs += bz * rhs_bstride;
-    TILE_STAMP_BEGIN();
+    TILE_STAMP_BEGIN(H * PL + H);
     const TileGeom g = tile_geom<PL - 2 * H, H, PL>(N);
     double av[W], mv[W - 1], md = 1.0, rmd = 1.0, ui = 0.0, ri = 0.0;
 #pragma unroll
@@ -1075,11 +1150,12 @@ k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t r
             lean_cheb_iter<0, PL>(a, live(k + 1), mv, md, rmd, r, om.w[k + 1], ym, yo);
         }
         if (k < K) lean_cheb_iter<1, PL>(a, live(k), mv, md, rmd, r, om.w[k], ym, yo);
+        TILE_STAMP_SWEPT();
         if (g.owned) {
-            ulow_[voff + g.i] = ui;
-            rdu_[voff + g.i] = r;
-            omid_[voff + g.i] = ym;
-            if (oold_) oold_[voff + g.i] = yo;
+            TILE_OUT(ulow_[voff + g.i], ui);
+            TILE_OUT(rdu_[voff + g.i], r);
+            TILE_OUT(omid_[voff + g.i], ym);
+            if (oold_) TILE_OUT(oold_[voff + g.i], yo);
         }
         TILE_STAMP_END(2);
         return;
@@ -1105,6 +1181,7 @@ k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t r
         __syncthreads();
         int t = io; io = im; im = in_; in_ = t;
     }
+    TILE_STAMP_SWEPT();
     if (g.owned) {
         ulow_[voff + g.i] = ui;
         rdu_[voff + g.i] = r;
@@ -1120,13 +1197,15 @@ k_tile_dudt_cheb(int n, int N, double h, MatRef A_ref, VecRef rhs_ref, int64_t r
 // appends the phase sums since the last dump to `path` (one line per kernel) and clears them
 void femfct_tile_phase_dump(const char* path) {
     static const char* names[4] = {"k_tile_build_jacobi", "k_tile_jacobi", "k_tile_dudt_cheb", "k_tile_cheb_flux_limit"};
-    unsigned long long h[4][4];
+    unsigned long long h[4][6];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile_phase), sizeof(h)) != hipSuccess) return;
     if (FILE* f = fopen(path, "a")) {
         for (int k = 0; k < 4; ++k)
             if (h[k][2])
-                fprintf(f, "%-24s launches %8llu  load phase %7.3f us  whole kernel %7.3f us  share %5.1f %%\n", names[k], h[k][2],
-                        0.01 * h[k][0] / h[k][2], 0.01 * h[k][1] / h[k][2], 100.0 * h[k][0] / (double)h[k][1]);
+                fprintf(f, "%-24s launches %8llu  load phase %7.3f us  whole kernel %7.3f us  share %5.1f %%  after the last sweep %6.3f us"
+                        "  (limiter: after the fluxes' barrier %6.3f us)\n", names[k], h[k][2], 0.01 * h[k][0] / h[k][2],
+                        0.01 * h[k][1] / h[k][2], 100.0 * h[k][0] / (double)h[k][1], 0.01 * (h[k][1] - h[k][3]) / h[k][2],
+                        k == 3 ? 0.01 * (h[k][1] - h[k][4]) / h[k][2] : 0.0);
         fclose(f);
     }
     memset(h, 0, sizeof(h));
@@ -1139,13 +1218,43 @@ void femfct_tile_phase_dump(const char* path) {
 // the LEAN template argument: 0 the loops as they were, 1 the lean loops, 2 the lean loops on the hexagonal cone
 static int tile_lean_mode(const femfct_ctx* ctx) { return ctx->tile_lean ? (ctx->tile_cone ? 2 : 1) : 0; }
 
+// ---- trimmed prologues and epilogues (FEMFCT_TILE_TRIM; the TRIM template argument of the four kernels) ----------------
+// The bits of the knob that launches of this context may take at all: the variants exist for the plain lean loops.
+static int tile_trim_mode(const femfct_ctx* ctx) { return tile_lean_mode(ctx) == 1 ? ctx->tile_trim & (TILE_TRIM_WAVES | TILE_TRIM_WT) : 0; }
+int femfct_tile_trim_mask(const femfct_ctx* ctx) { return tile_trim_mode(ctx); }
+static void tile_trim_count(femfct_ctx* ctx, int trim) {      // (flags, not counts: the launchers run for a context's lifetime)
+    if (trim & TILE_TRIM_WAVES) ctx->trim_seen[0] = 1;
+    if (trim & TILE_TRIM_WT) ctx->trim_seen[1] = 1;
+}
+
+// calls f with the mask (0, 1, 8 or 9) as a compile-time constant
+template <class F>
+static void with_trim(int trim, F&& f) {
+    switch (trim) {
+    case TILE_TRIM_WAVES: f(std::integral_constant<int, TILE_TRIM_WAVES>()); break;
+    case TILE_TRIM_WT: f(std::integral_constant<int, TILE_TRIM_WT>()); break;
+    case TILE_TRIM_WAVES | TILE_TRIM_WT: f(std::integral_constant<int, TILE_TRIM_WAVES | TILE_TRIM_WT>()); break;
+    default: f(std::integral_constant<int, 0>()); break;
+    }
+}
+
+// Bit 1: slots per array when the Jacobi launches of a deferred-test solve publish per owning wave; 0: per workgroup as
+// before (knob off, other loops, or more slots than an array holds)
+int femfct_tile_wave_slots(const femfct_ctx* ctx, const TilePlan& pl) {
+    if (!(tile_trim_mode(ctx) & TILE_TRIM_WAVES)) return 0;
+    const int64_t slots = (int64_t)pl.tiles * pl.tiles * tile_owning_waves(pl.H);
+    return slots <= FEMFCT_MAX_PARTIALS ? (int)slots : 0;
+}
+
 // launch 0 with the operator construction fused in (latency regime; needs >= 2 launches in total because
 // ||b|| is reduced by launch 1).  Later launches: femfct_enqueue_tile_jacobi(..., bn_launch = 1, g_build = tiles^2).
 // pre: A is the pre-built L_k sequence (femfct_enqueue_low_seq; Nm must be null), D_k is not stored.
 int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, MatRef A, const double* Nm, int32_t nshared,
                                      VecRef rhs, int64_t rhs_bstride, VecRef u_n, int64_t u_bstride, double dt,
-                                     int32_t batch, bool pre) {
+                                     int32_t batch, bool pre, bool wave_slots) {
     if (pre && Nm) return femfct_fail(ctx, FEMFCT_ERR_INVALID, "pre-built low-order operator with a non-flux matrix");
+    const int trim = tile_trim_mode(ctx) & ((wave_slots ? TILE_TRIM_WAVES : 0) | TILE_TRIM_WT);
+    tile_trim_count(ctx, trim);
     dim3 grid(pl.tiles, pl.tiles, batch);
     femfct_prof_begin(ctx, KC_JACOBI);
     auto go = [&](auto kernel) {
@@ -1154,6 +1263,13 @@ int femfct_enqueue_tile_build_jacobi(femfct_ctx* ctx, const TilePlan& pl, MatRef
     };
     with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
         constexpr int H = decltype(h)::value;
+        if (trim) {             // (lean loops without the cone: tile_trim_mode)
+            with_trim(trim, [&](auto t) {
+                constexpr int TRIM = decltype(t)::value;
+                if (pre) go(k_tile_build_jacobi<H, 1, 1, TRIM>); else go(k_tile_build_jacobi<H, 0, 1, TRIM>);
+            });
+            return;
+        }
         with_constant<0, 2>(tile_lean_mode(ctx), [&](auto l) {
             constexpr int LEAN = decltype(l)::value;
             if (pre) go(k_tile_build_jacobi<H, 1, LEAN>); else go(k_tile_build_jacobi<H, 0, LEAN>);
@@ -1175,8 +1291,11 @@ int femfct_enqueue_low_seq(femfct_ctx* ctx, const double* A, double* L, double* 
 }
 
 int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double* L, const double* b, double* xa,
-                               double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch, int defer) {
+                               double* xb, int launch, int g_build, int32_t batch, bool last, int bn_launch, int defer, bool wave_slots) {
     const bool big = femfct_tile_big(ctx, pl);
+    // (the owning-wave epilogue belongs to deferred-test launches)
+    const int trim = big ? 0 : tile_trim_mode(ctx) & (((wave_slots && defer) ? TILE_TRIM_WAVES : 0) | TILE_TRIM_WT);
+    tile_trim_count(ctx, trim);
     double* bigp = big ? ctx->d_bigpart : nullptr;
     double* pk = ((last || defer) && !big) ? ctx->d_partk : nullptr;
     dim3 grid(pl.tiles, pl.tiles, batch);
@@ -1193,6 +1312,16 @@ int femfct_enqueue_tile_jacobi(femfct_ctx* ctx, const TilePlan& pl, const double
         } else {
             with_constant<8, TILE_HMAX>(pl.H, [&](auto h) {
                 constexpr int H = decltype(h)::value;
+                if constexpr (LEAN == 1) {
+                    if (trim) {
+                        with_trim(trim, [&](auto t) {
+                            constexpr int TRIM = decltype(t)::value;
+                            if constexpr (!(TRIM & TILE_TRIM_WAVES)) { if (pk && !defer) { go(k_tile_jacobi<H, 1, 0, 1, TRIM>, 0); return; } }
+                            go(k_tile_jacobi<H, 0, 0, 1, TRIM>, defer);
+                        });
+                        return;
+                    }
+                }
                 if (pk && !defer) go(k_tile_jacobi<H, 1, 0, LEAN>, 0); else go(k_tile_jacobi<H, 0, 0, LEAN>, defer);
             });
         }
@@ -1212,8 +1341,12 @@ void femfct_launch_reduce_resid(femfct_ctx* ctx, int64_t count, int launch, int3
 // mid = d_y0, old = d_y2), e.g. fused with the limiter; 0 is stored when nothing remains.
 int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, MatRef A, VecRef rhs, int64_t rhs_bstride, double* ulow,
                                   int budget_units, int part_count, int iters_per_unit, int exact_k, int iters,
-                                  const double* omegas, double md_scale, int32_t batch, int* tail_first) {
+                                  const double* omegas, double md_scale, int32_t batch, int* tail_first, bool wave_slots) {
     constexpr int H = 10;
+    const int trim = tile_trim_mode(ctx) & (((wave_slots && exact_k < 0) ? TILE_TRIM_WAVES : 0) | TILE_TRIM_WT);
+    if (wave_slots && !(tile_trim_mode(ctx) & TILE_TRIM_WAVES))
+        return femfct_fail(ctx, FEMFCT_ERR_INVALID, "per-wave partials outside the trimmed lean launches");
+    tile_trim_count(ctx, trim);
     const int T = TILE_L - 2 * H, t = (ctx->N + T - 1) / T;
     const bool fit = femfct_tile_fit(ctx, batch);
     const int tl = fit ? (ctx->N + 5) / 6 : t;           // workgroups per side of this launch (the chained ones keep T = 12)
@@ -1233,7 +1366,12 @@ int femfct_enqueue_tile_dudt_cheb(femfct_ctx* ctx, MatRef A, VecRef rhs, int64_t
     // (the mass row from the geometry rides with the lean loops: FEMFCT_TILE_LEAN=0 is the kernel as it was)
     with_constant<0, 1>(ctx->tile_lean && femfct_geom_mass(ctx), [&](auto gm) {
         constexpr int GM = decltype(gm)::value;
-        if (fit) {
+        if (trim) {             // (lean loops without the cone: tile_trim_mode)
+            with_trim(trim, [&](auto t) {
+                constexpr int TRIM = decltype(t)::value;
+                if (fit) go(k_tile_dudt_cheb<1, GM, 26, TRIM>, 26); else go(k_tile_dudt_cheb<1, GM, TILE_L, TRIM>, TILE_L);
+            });
+        } else if (fit) {
             if (ctx->tile_cone) go(k_tile_dudt_cheb<2, GM, 26>, 26); else go(k_tile_dudt_cheb<1, GM, 26>, 26);
         } else if constexpr (GM) {
             if (ctx->tile_cone) go(k_tile_dudt_cheb<2, 1, TILE_L>, TILE_L); else go(k_tile_dudt_cheb<1, 1, TILE_L>, TILE_L);
@@ -1301,6 +1439,8 @@ int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const 
     for (int k = k_first; k <= k_last; ++k) om.w[k - k_first] = omegas[k - 1];
     const bool fit = femfct_tile_fit(ctx, batch);
     const int t = fit ? (ctx->N + 5) / 6 : (ctx->N + 7) / 8;
+    const bool wt = (tile_trim_mode(ctx) & TILE_TRIM_WT) != 0;
+    tile_trim_count(ctx, wt ? TILE_TRIM_WT : 0);
     femfct_prof_begin(ctx, KC_FLUX);
     auto go = [&](auto kernel, int PL) {
         hipLaunchKernelGGL(kernel, dim3(t, t, batch), dim3((PL * PL + WAVE - 1) / WAVE * WAVE), 0, ctx->stream, ctx->n, ctx->N,
@@ -1308,7 +1448,10 @@ int femfct_enqueue_tile_cheb_flux_limit(femfct_ctx* ctx, const double* b, const 
     };
     with_constant<0, 1>(femfct_geom_mass(ctx), [&](auto gm) {
         constexpr int GM = decltype(gm)::value;
-        if (fit) {
+        if (wt) {               // (lean loops without the cone: tile_trim_mode)
+            if (fit) go(k_tile_cheb_flux_limit<GM, 1, 30, TILE_TRIM_WT>, 30);
+            else go(k_tile_cheb_flux_limit<GM, 1, TILE_L, TILE_TRIM_WT>, TILE_L);
+        } else if (fit) {
             if (ctx->tile_cone) go(k_tile_cheb_flux_limit<GM, 2, 30>, 30); else go(k_tile_cheb_flux_limit<GM, 1, 30>, 30);
         } else {
             with_constant<0, 2>(tile_lean_mode(ctx), [&](auto l) { go(k_tile_cheb_flux_limit<GM, decltype(l)::value, TILE_L>, TILE_L); });

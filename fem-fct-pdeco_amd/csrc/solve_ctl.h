@@ -9,7 +9,8 @@
 // reduced by the kernel behind them, in one pass, and the verdict the in-launch tests would have reached is
 // reconstructed (the first launch whose residual passed gives the sweep count the host budgets from).  Split in two so
 // that the caller (wave 0 of workgroup 0 of k_tile_dudt_cheb) can request the partials before its tile work and
-// publish after it: no LDS, no barrier -- the publish is a handful of lane shifts at the kernel's end.  What differs
+// publish after it: deferred_test_load and deferred_test_publish use no LDS and no barrier -- the publish is a handful of
+// lane shifts at the kernel's end.  deferred_test_load_wide does: every thread of the workgroup must call it.  What differs
 // from the in-launch test: had an earlier launch already converged, the later ones ran nevertheless (their sweeps only
 // lower the residual further; the iterate returned is the budget-parity one).
 // Residual maxima: launch 0 at p[0 .. G), launch s >= 1 at partk[s * FEMFCT_MAX_PARTIALS ..).
@@ -33,6 +34,48 @@ __device__ __forceinline__ DeferredPartials deferred_test_load(const double* p, 
         }
     }
     return d;
+}
+
+// The same for launches that end with their owning waves (FEMFCT_TILE_TRIM bit 1): S = workgroups x owning waves slots per
+// array, several times the count above, so every wave of the workgroup loads a share (one or two loads per lane and array
+// instead of a dozen in a chain) and the waves' maxima and minimum meet in `lds` (6 doubles per wave).  Returned as
+// partials in the first lanes of wave 0, which deferred_test_publish reduces as it does the loaded ones.  Max and min are
+// exact in any order and carry a NaN through every stage: the same bits as the per-workgroup partials give.
+__device__ __forceinline__ DeferredPartials deferred_test_load_wide(const double* p, const double* partk, int S, int units,
+                                                                    double* lds) {
+    static_assert(FEMFCT_DEFER_MAX_UNITS + 2 == 6, "lds layout");
+    DeferredPartials d;
+#pragma unroll
+    for (int s = 0; s < FEMFCT_DEFER_MAX_UNITS; ++s) d.r[s] = 0.0;
+    d.bn = 0.0; d.rs = INFINITY;
+#pragma unroll 2
+    for (int k = threadIdx.x; k < S; k += blockDim.x) {
+        d.r[0] = nan_max(d.r[0], p[k]);
+#pragma unroll
+        for (int s = 1; s < FEMFCT_DEFER_MAX_UNITS; ++s)
+            if (s < units) d.r[s] = nan_max(d.r[s], partk[(int64_t)s * FEMFCT_MAX_PARTIALS + k]);
+        d.bn = nan_max(d.bn, p[2 * FEMFCT_MAX_PARTIALS + k]);
+        d.rs = nan_min(d.rs, p[3 * FEMFCT_MAX_PARTIALS + k]);
+    }
+    const int wid = threadIdx.x / WAVE, nw = (blockDim.x + WAVE - 1) / WAVE;
+#pragma unroll
+    for (int s = 0; s < FEMFCT_DEFER_MAX_UNITS; ++s) d.r[s] = wave_reduce(d.r[s], OpMax());
+    d.bn = wave_reduce(d.bn, OpMax());
+    d.rs = wave_reduce(d.rs, OpMin());
+    if (threadIdx.x % WAVE == 0) {
+#pragma unroll
+        for (int s = 0; s < FEMFCT_DEFER_MAX_UNITS; ++s) lds[6 * wid + s] = d.r[s];
+        lds[6 * wid + 4] = d.bn;
+        lds[6 * wid + 5] = d.rs;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nw) {
+#pragma unroll
+        for (int s = 0; s < FEMFCT_DEFER_MAX_UNITS; ++s) d.r[s] = lds[6 * threadIdx.x + s];
+        d.bn = lds[6 * threadIdx.x + 4];
+        d.rs = lds[6 * threadIdx.x + 5];
+    }
+    return d;      // (the other lanes of wave 0 hold their wave's own result once more: harmless to a maximum or minimum)
 }
 
 __device__ __forceinline__ void deferred_test_publish(StepCtl* ctl, DeferredPartials d, int units, int iters_per_unit,

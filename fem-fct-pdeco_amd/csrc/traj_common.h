@@ -44,7 +44,7 @@ int femfct_run_graph_reps(femfct_ctx* ctx, femfct_ctx::GraphKey key, int reps, i
     key.push_back(key_bits((int32_t)ctx->solver));
     key.push_back(key_bits(ctx->low_src));                 // the tile step reads pre-built L_k / D_k (femfct_prebuild_low)
     key.push_back(key_bits(ctx->low_dt));
-    key.push_back(key_bits((int32_t)(ctx->tile_lean | ctx->tile_cone << 1 | ctx->tile_fit << 2)));   // other sweep loops / patches of the tile kernels are captured
+    key.push_back(key_bits((int32_t)(ctx->tile_lean | ctx->tile_cone << 1 | ctx->tile_fit << 2 | femfct_tile_trim_mask(ctx) << 3)));   // other sweep loops / patches of the tile kernels are captured
     // delta: the time-level step of this kind of sweep (+1 forward, -1 adjoint).  Step r is enqueued with its level
     // offset baked into every level-indirected reference (lref, MatRef::level_off); the device counters move once, in
     // the last step of the graph -- no per-step ticket / counter update on the critical path of the other R - 1 steps.

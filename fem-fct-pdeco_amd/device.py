@@ -159,6 +159,14 @@ class Context:
         return {"jacobi_kernel": kinds.get(out[0], "?"), "jacobi_walkers": int(out[1]), "cheb_interior_patches": int(out[2]),
                 "halo": int(out[3])}
 
+    def tile_trim_info(self) -> dict:
+        """What the latency-regime tile launchers made of FEMFCT_TILE_TRIM (diagnostic): the bits in effect, launches enqueued
+        with the owning-wave epilogue and with write-through stores, partial slots per array of the last deferred-test solve
+        (0: one per workgroup)."""
+        out = (C.c_int32 * 4)()
+        check(self.handle, lib.femfct_tile_trim_info(self.handle, out))
+        return {"mask": int(out[0]), "wave_launches": int(out[1]), "wt_launches": int(out[2]), "wave_slots": int(out[3])}
+
     def graph_replay_active(self) -> bool:
         """False while sweeps are enqueued kernel by kernel: graphs off, per-class profiling, or rocprofv3 attached."""
         v = C.c_int(0)

@@ -97,6 +97,10 @@ int         femfct_set_graphs(femfct_ctx* ctx, int enable); /* hipGraph replay o
  * 1 one workgroup per patch, 2 k_strip4_jacobi_walk, 3 k_strip_jacobi_pair_walk), out[1] its walkers, out[2] interior patches
  * per side of the split Chebyshev launch (0: not split), out[3] halo depth.  No reference counterpart (diagnostic). */
 int         femfct_launch_info(const femfct_ctx* ctx, int32_t* out4_host);
+/* What the latency-regime tile launchers made of FEMFCT_TILE_TRIM: out[0] the bits in effect, out[1] / out[2] whether a launch was
+ * enqueued with the owning-wave epilogue / with write-through stores, out[3] partial slots per array of the most recent deferred-test
+ * solve (0: one per workgroup).  No reference counterpart (diagnostic). */
+int         femfct_tile_trim_info(const femfct_ctx* ctx, int32_t* out4_host);
 int         femfct_graph_replay_active(const femfct_ctx* ctx, int* active_host);
 /* 1 when the most recent femfct_solidbody_forward / _adjoint evaluated the rotation operator from the node positions
  * (large meshes, operator from femfct_assemble_rotation), 0 when it loaded the stored array.  Diagnostic. */
