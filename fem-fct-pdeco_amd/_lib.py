@@ -172,6 +172,7 @@ SIGNATURES = {
     "femfct_prox_trials": (C.c_int, [_p, _p, _p, _p, _d, _i, _d, _d, _d, C.c_int64, _p, _p]),
     "femfct_l1_norm_Q": (C.c_int, [_p, _p, _i, _d, _p, _i]),
     "femfct_sparse_trial_stats": (C.c_int, [_p, _p, _p, _i, _i, _d, _p, _p, _p]),
+    "femfct_budget_trials": (C.c_int, [_p, _p, _p, _p, _d, _i, _d, _d, _d, _d, _i, _d, _p, _p, _p, _p, _p]),
     "femfct_ensemble_drift_gradient_rhs": (C.c_int, [_p, _p, _p, _p, _p, _i, _d, _d, _d, _p, _i]),
     "femfct_ensemble_costs": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _d, _p, _p, _p]),
     "femfct_initial_trials": (C.c_int, [_p, _p, _p, _p, _i, _d, _d, _p, _i]),

@@ -291,6 +291,12 @@ FEMFCT_INTERNAL int femfct_ensure_scratch(femfct_ctx* ctx, size_t doubles);
 // out_dev[b] (+)= scale * sum_l w_l sum_blocks partial[(b*levels + l)*G + block], w_l the trapezoid's when trapezoid != 0
 FEMFCT_INTERNAL void femfct_enqueue_reduce_levels(femfct_ctx* ctx, int32_t batch, int levels, int G, const double* partial,
                                                   int trapezoid, double scale, int accumulate, double* out_dev);
+// femfct_budget_trials' search (kernels_budget.hip): the host's verdict on one round's read-back for one trial
+#define BUDGET_POINTS 15                  // interior points of a round's 16-way split of the bracket
+#define BUDGET_SUMS (BUDGET_POINTS + 3)   // + S_fix, S_lin, W (trapezoid-folded); the count is folded apart, unweighted
+#define BUDGET_VALS (BUDGET_SUMS + 1)     // doubles read back per trial and round
+#define BUDGET_MAX_ROUNDS 16
+FEMFCT_INTERNAL bool femfct_budget_narrow(double* a, double* b, const double* v, double budget, double* th);
 
 // graph-key helpers
 static inline uint64_t key_bits(const void* p) { return (uint64_t)(uintptr_t)p; }

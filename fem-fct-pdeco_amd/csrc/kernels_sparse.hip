@@ -10,17 +10,9 @@
 // femfct_l2_norm_sq_Q bit for bit.
 #include "femfct_internal.h"
 #include "device_utils.h"
+#include "prox_device.h"      // prox_value
 
 namespace {
-
-// clip(soft_threshold(c + s d, s alpha), lo, hi), evaluated in this order with no contraction (-ffp-contract=off), as
-// k_clip_axpy evaluates its clip; alpha = 0 gives k_clip_axpy's value (+0.0 where that has -0.0)
-__device__ __forceinline__ double prox_value(double c, double s, double d, double tau, double lo, double hi) {
-    const double x = c + s * d;
-    const double t = fabs(x) - tau;
-    const double v = (t > 0) ? copysign(t, x) : 0.0;
-    return fmin(fmax(v, lo), hi);
-}
 
 // V neighbouring doubles moved as one access: 16 bytes for V = 2
 template <int V> struct Pack { double v[V]; };

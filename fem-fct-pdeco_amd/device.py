@@ -628,6 +628,22 @@ class Context:
         check(self.handle, lib.femfct_prox_trials(self.handle, dptr(c), dptr(d), dptr(g), float(s0), int(K), float(alpha),
                                                   float(c_lower), float(c_upper), int(count), dptr(c_out), dptr(src_out)))
 
+    def budget_trials(self, c, d, s0, K, alpha, budget, c_lower, c_upper, num_steps, dt, c_out, src_out=None, g=None):
+        """``prox_trials`` under the control budget ||c_t||_{1,h} <= ``budget``: c_out[t] = clip(soft_threshold(c + s_t d,
+        s_t alpha + lam[t])), lam[t] = 0.0 exactly (and ``prox_trials``' bits) where that trial is within the budget, else
+        the root of ||c_out[t]||_{1,h} = budget -- value by value the projection onto {box, ||.||_{1,h} <= budget} in the
+        nodal-quadrature inner product (weights dt w_l ml_i), the metric of the prox.  ``d`` None (K = 1): the projection of
+        ``c`` itself.  The box must contain 0.  Returns ``(lam, l1, rounds)``: the multipliers, ``l1_norm_Q`` of the
+        written trials bit for bit, the search rounds used (int32, <= 16).  The same bits on every call; a NaN or Inf in
+        ``c`` or ``d`` raises.  Synchronises."""
+        k = max(int(K), 1)
+        lam, l1, rounds = np.empty(k), np.empty(k), np.empty(k, dtype=np.int32)
+        check(self.handle, lib.femfct_budget_trials(self.handle, dptr(c), dptr(d), dptr(g), float(s0), int(K), float(alpha),
+                                                    float(budget), float(c_lower), float(c_upper), int(num_steps), float(dt),
+                                                    dptr(c_out), dptr(src_out), _host_ptr(lam), _host_ptr(l1),
+                                                    _host_ptr(rounds)))
+        return lam, l1, rounds
+
     def l1_norm_Q(self, a, num_steps, dt, batch=1) -> np.ndarray:
         """dt sum_l w_l sum_i ml_i |a_{l,i}| of every batch member: the nodal-quadrature L1(Q) norm (the trapezoid weights
         of ``l2_norm_sq_Q``, the lumped mass).  The same bits on every call."""

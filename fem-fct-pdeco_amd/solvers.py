@@ -1830,12 +1830,16 @@ def lbfgs_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, c_lower,
 # s_t alpha |.| + the box indicator.  It is the nodal discretisation of the continuous proximal-gradient step, the same
 # approximation the loops above make when they clip value by value under the consistent-mass metric.
 def _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha, c_lower, c_upper, max_iters, gam, s0, K,
-                  tol):
+                  tol, budget=None, proj=None):
     """The iteration both proximal-gradient loops share.  ``gradient()`` runs the adjoint at the current (c, u) and returns
     the device direction d = -g; ``trial_costs(d)`` writes the K trial controls into ``cB``, runs their states as one
-    batch and returns the K smooth costs J(S(c_t), c_t); ``take(t)`` makes trial t the iterate."""
+    batch and returns the K smooth costs J(S(c_t), c_t); ``take(t)`` makes trial t the iterate.  With a ``budget`` the
+    residual trial is ``budget_trials``' and ``trial_costs`` leaves its trials' multipliers and search rounds in
+    ``proj["lam"]``, ``proj["rounds"]``; everything else is the same code."""
     hist = dict(cost=[], cost_smooth=[], l1=[], nonzero_fraction=[], residual=[], armijo_k=[], step=[], armijo_margin=[],
                 rel_change=[], sweeps=[], wall=[], wall0=time.perf_counter(), stalled=False)
+    if budget is not None:
+        hist.update(multiplier=[], budget_used=[], projection_rounds=[])
     svals = [s0 * (1 / 2 ** k) for k in range(K)]
     F = J0 + alpha * float(ctx.l1_norm_Q(c, Nt, dt)[0])
     hist["cost0"] = F
@@ -1843,7 +1847,10 @@ def _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha
     for _ in range(max_iters):
         d = gradient()
         sweeps += 1
-        ctx.prox_trials(c, d, 1.0, 1, alpha, c_lower, c_upper, tl, cB)       # prox(c - g; tau = alpha), in trial 0's place
+        if budget is None:
+            ctx.prox_trials(c, d, 1.0, 1, alpha, c_lower, c_upper, tl, cB)   # prox(c - g; tau = alpha), in trial 0's place
+        else:
+            ctx.budget_trials(c, d, 1.0, 1, alpha, budget, c_lower, c_upper, Nt, dt, cB)
         residual = float(ctx.l2_norm_sq_Q(cB, c, Nt, dt)[0])
         J = trial_costs(d)
         l1, dist, nnz = ctx.sparse_trial_stats(cB, c, K, Nt, dt)
@@ -1864,6 +1871,10 @@ def _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha
                        ("step", svals[found]), ("armijo_margin", margins), ("rel_change", abs(F - Ft) / abs(F)),
                        ("sweeps", sweeps), ("wall", time.perf_counter())):
             hist[key].append(v)
+        if budget is not None:
+            hist["multiplier"].append(float(proj["lam"][found]))
+            hist["budget_used"].append(float(l1[found]) / budget)
+            hist["projection_rounds"].append(int(proj["rounds"][found]))
         F = Ft
         if tol is not None and hist["rel_change"][-1] < tol:
             break
@@ -1872,8 +1883,44 @@ def _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha
     return hist
 
 
-def _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time):
-    """the argument validation of the L-BFGS loops, and alpha >= 0; returns (K, u0, uhat, c0) as flat float64 arrays"""
+def _need_budget(budget, c_lower, c_upper):
+    if not (np.isfinite(budget) and budget > 0):
+        raise ValueError(f"budget = {budget}: must be finite and > 0 (None: no budget; for 'unbounded' pass a large number)")
+    if not c_lower <= 0 <= c_upper:
+        raise ValueError(f"a budget needs a box that contains 0, got [{c_lower}, {c_upper}]")
+
+
+def _need_within_budget(ctx, c, Nt, dt, budget):
+    """the loops start from a control inside the budget (they never project the start themselves)"""
+    l1 = float(ctx.l1_norm_Q(c, Nt, dt)[0])
+    if not l1 <= budget * (1 + 1e-12):
+        raise ValueError(f"c0 has ||c0||_(1,h) = {l1} > budget = {budget}: start from project_onto_budget(prob, c0, budget, "
+                         f"c_lower, c_upper)[0]")
+
+
+def project_onto_budget(prob, c, budget, c_lower, c_upper):
+    """The projection of the control trajectory ``c`` (host array, (num_steps + 1) * n values) onto
+    {c_lower <= c <= c_upper, ||c||_{1,h} <= budget}, c_lower <= 0 <= c_upper, in the nodal-quadrature inner product
+    sum dt w_l ml_i a_{l,i} b_{l,i} -- the metric in which the prox of the L1 loops is taken, not the consistent-mass Q
+    metric of their Armijo distance.  Returns ``(P, lam)``: P = clip(soft_threshold(c, lam)) as a host array and the
+    multiplier, 0.0 where clip(c) is within the budget.  ``Context.budget_trials`` with d = None, K = 1."""
+    c = np.asarray(c, dtype=np.float64).ravel()
+    if c.size != prob.tlen:
+        raise ValueError(f"c of {c.size} values, expected {prob.tlen}")
+    _need_budget(budget, c_lower, c_upper)
+    ctx = prob.ctx
+    cd, out = ctx.array(c), ctx.empty(prob.tlen)
+    try:
+        lam, _, _ = ctx.budget_trials(cd, None, 1.0, 1, 0.0, budget, c_lower, c_upper, prob.num_steps, prob.dt, out)
+        return out.download(), float(lam[0])
+    finally:
+        cd.free()
+        out.free()
+
+
+def _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time, budget=None):
+    """the argument validation of the L-BFGS loops, alpha >= 0 and the budget's; returns (K, u0, uhat, c0) as flat float64
+    arrays"""
     snap = _need_obs(optim, obs)
     alltime = optim == "alltime" or snap
     n, Nt, tl = prob.n, prob.num_steps, prob.tlen
@@ -1884,6 +1931,8 @@ def _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, 
         raise ValueError(f"alpha = {alpha}: must be >= 0")
     if not c_lower <= c_upper:
         raise ValueError(f"c_lower = {c_lower} > c_upper = {c_upper}")
+    if budget is not None:
+        _need_budget(budget, c_lower, c_upper)
     uhat = np.asarray(uhat, dtype=np.float64).ravel()
     if uhat.size != (tl if alltime else n):
         raise ValueError(f"target of {uhat.size} values, expected {tl if alltime else n} for optim='{optim}'")
@@ -1901,7 +1950,7 @@ def _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, 
 
 
 def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_upper, iters, gam=1e-4, s0=1.0,
-                   max_armijo=10, tol=None, optim="finaltime", obs=None, control_time=None):
+                   max_armijo=10, tol=None, optim="finaltime", obs=None, control_time=None, budget=None):
     """Proximal gradient descent for the drift-control problem with an L1 term: minimises
     F(c) = J(S(c), c) + alpha ||c||_{1,h} over the box, J the cost of :func:`lbfgs_solidbody` and
     ||c||_{1,h} = dt sum_l w_l sum_i ml_i |c_{l,i}| (``Context.l1_norm_Q``).  Per iteration, at the control c with
@@ -1922,8 +1971,20 @@ def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_u
     (F_t - F + gam/s_t dist_t) / |F|), ``armijo_margin_min``, ``rel_change``, ``sweeps`` (as the L-BFGS loops count
     them), ``wall``, ``wall0``, ``cost0``, ``stalled``, ``iterations``.  Every list has one entry per accepted step: an
     iteration that stalls, as in the L-BFGS loops, leaves no entry (its residual and the margins of its ``max_armijo``
-    rejected trials are not kept, so a run that stalls at once has ``armijo_margin_min`` None)."""
-    K, u0, uhat, c0 = _prox_arguments(prob, u0, uhat, c0, None, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time)
+    rejected trials are not kept, so a run that stalls at once has ``armijo_margin_min`` None).
+
+    ``budget`` B (None: none; else finite and > 0, with c_lower <= 0 <= c_upper) adds the hard constraint
+    ||c||_{1,h} <= B: the residual trial and the K trials become ``Context.budget_trials``',
+    c_t = clip(soft_threshold(c - s_t g, s_t alpha + lam_t)) with lam_t >= 0 the smallest value that meets the budget --
+    the prox of s_t alpha ||.||_{1,h} + the indicator of {box, ||.||_{1,h} <= B} in the nodal-quadrature metric (weights
+    dt w_l ml_i), the metric the prox above is already taken in.  The Armijo test, its consistent-mass distance
+    ||c_t - c||^2_Q, the statistics and the batched sweep are unchanged; ``alpha = 0`` is projected gradient onto the
+    budget set.  One lam per trial and a value-by-value map: with ``control_time`` the iterates stay piecewise constant
+    bit for bit.  c0 must satisfy ||c0||_{1,h} <= B (1 + 1e-12) (ValueError; see :func:`project_onto_budget`).  The
+    history gains ``multiplier`` (lam of the accepted trial; 0.0: the budget was slack), ``budget_used`` (l1 / B) and
+    ``projection_rounds``.  Not combined with zones, the L-BFGS, ensemble, lockstep or initial-state loops."""
+    K, u0, uhat, c0 = _prox_arguments(prob, u0, uhat, c0, None, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time,
+                                      budget)
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     bufs = []
 
@@ -1935,6 +1996,8 @@ def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_u
     try:
         u, p, d, rhs = alloc(tl), alloc(tl), alloc(tl), alloc(tl, False)
         c = alloc(tl, False).upload(c0)
+        if budget is not None:
+            _need_within_budget(ctx, c, Nt, dt, budget)
         uh = alloc(uhat.size, False).upload(uhat)
         uhB = alloc(K * uhat.size, False)
         cB, uB = alloc(K * tl), alloc(K * tl)
@@ -1946,6 +2009,7 @@ def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_u
         cost = lambda uu, hh, cc, b: prob.cost(uu, hh, cc, beta, optim, batch=b, obs=obs)
         prob.forward(c, u, batch=1)
         J0 = float(cost(u, uh, c, 1)[0])
+        proj = {}
 
         def gradient():
             prob.adjoint(c, u, uh, p, optim, batch=1, obs=obs)
@@ -1956,7 +2020,10 @@ def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_u
             return d
 
         def trial_costs(dirv):
-            ctx.prox_trials(c, dirv, s0, K, alpha, c_lower, c_upper, tl, cB)
+            if budget is None:
+                ctx.prox_trials(c, dirv, s0, K, alpha, c_lower, c_upper, tl, cB)
+            else:
+                proj["lam"], _, proj["rounds"] = ctx.budget_trials(c, dirv, s0, K, alpha, budget, c_lower, c_upper, Nt, dt, cB)
             prob.forward(cB, uB, batch=K)
             return cost(uB, uhB, cB, K)
 
@@ -1965,7 +2032,7 @@ def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_u
             u.copy_from(uB, tl, src_off=t * tl)
 
         hist = _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha, c_lower, c_upper, int(iters),
-                             gam, s0, K, tol)
+                             gam, s0, K, tol, budget, proj)
         return u.download(), p.download(), c.download(), hist
     finally:
         for a in bufs:
@@ -1973,14 +2040,16 @@ def prox_solidbody(prob: SolidBodyDrift, u0, uhat, c0, beta, alpha, c_lower, c_u
 
 
 def prox_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, alpha, c_lower, c_upper, g=None, optim="alltime",
-                        gam=1e-4, s0=1.0, max_armijo=10, tol=None, max_iters=1000, obs=None, control_time=None):
+                        gam=1e-4, s0=1.0, max_armijo=10, tol=None, max_iters=1000, obs=None, control_time=None, budget=None):
     """Proximal gradient descent for the linear source-control problem (:class:`LinearSourceControl`,
     :class:`LinearReactionSourceControl`) with an L1 term: the iteration of :func:`prox_solidbody` with the gradient
     -descent_direction = beta c - p, the trial controls and sources g + c_t of ``femfct_prox_trials`` in one launch and the
     ``max_armijo`` trial states as one batched sweep, as :func:`lbfgs_source_control` runs them.  ``alpha = 0`` is
     ``lbfgs_source_control(memory=0)``'s iteration.  Runs ``max_iters`` iterations, or until rel_change < ``tol``.
-    Arguments as lbfgs_source_control; return value and history as prox_solidbody."""
-    K, u0, uhat, c0 = _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time)
+    Arguments as lbfgs_source_control; return value, history and ``budget`` (the control budget ||c||_{1,h} <= B: projection
+    in the nodal-quadrature metric, Armijo distance in the consistent-mass Q norm) as prox_solidbody."""
+    K, u0, uhat, c0 = _prox_arguments(prob, u0, uhat, c0, g, alpha, c_lower, c_upper, max_armijo, optim, obs, control_time,
+                                      budget)
     snap = _need_obs(optim, obs)
     ctx, n, Nt, dt, tl = prob.ctx, prob.n, prob.num_steps, prob.dt, prob.tlen
     bufs = []
@@ -2003,8 +2072,11 @@ def prox_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, alpha, c_
             uhB.copy_from(uh, uhat.size, dst_off=k * uhat.size)
         if gd is not None:
             ctx.axpby(tl, 1.0, gd, 1.0, c, src)
+        if budget is not None:
+            _need_within_budget(ctx, c, Nt, dt, budget)
         prob.state(src, u, batch=1)
         J0 = float(prob.cost(u, uh, c, beta, optim, batch=1, obs=obs)[0])
+        proj = {}
 
         def gradient():
             prob.adjoint_state(u, uh, p, optim, batch=1, obs=obs) if snap else prob.adjoint_state(u, uh, p, optim, batch=1)
@@ -2015,7 +2087,11 @@ def prox_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, alpha, c_
             return d
 
         def trial_costs(dirv):
-            ctx.prox_trials(c, dirv, s0, K, alpha, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
+            if budget is None:
+                ctx.prox_trials(c, dirv, s0, K, alpha, c_lower, c_upper, tl, cB, None if gd is None else srcB, g=gd)
+            else:
+                proj["lam"], _, proj["rounds"] = ctx.budget_trials(c, dirv, s0, K, alpha, budget, c_lower, c_upper, Nt, dt, cB,
+                                                                   None if gd is None else srcB, g=gd)
             prob.state(srcB, uB, batch=K)
             return prob.cost(uB, uhB, cB, beta, optim, batch=K, obs=obs)
 
@@ -2024,7 +2100,7 @@ def prox_source_control(prob: LinearSourceControl, u0, uhat, c0, beta, alpha, c_
             u.copy_from(uB, tl, src_off=t * tl)
 
         hist = _prox_iterate(ctx, tl, Nt, dt, c, cB, J0, gradient, trial_costs, take, alpha, c_lower, c_upper,
-                             int(max_iters), gam, s0, K, tol)
+                             int(max_iters), gam, s0, K, tol, budget, proj)
         return u.download(), p.download(), c.download(), hist
     finally:
         for a in bufs:

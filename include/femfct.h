@@ -449,6 +449,21 @@ int femfct_l1_norm_Q(femfct_ctx* ctx, const double* a_dev, int32_t num_steps, do
  * c_ref), both bit for bit, and nnz_host[t] = the number of values of c_t that are != 0.  Synchronises. */
 int femfct_sparse_trial_stats(femfct_ctx* ctx, const double* c_trials_dev, const double* c_ref_dev, int32_t K,
                               int32_t num_steps, double dt, double* l1_host, double* dist_host, int64_t* nnz_host);
+/* The K trial controls of a proximal step under a control budget ||c||_{1,h} <= budget (solvers.prox_solidbody and
+ * prox_source_control with budget=; added after ABI version 5, backward compatible).  For t < K, s_t = s0 * (1 / 2^t),
+ * tau_t = s_t*alpha, x_t = c + s_t*d:
+ *   c_out[t] = clip(soft_threshold(x_t, tau_t + lambda_t), c_lower, c_upper)      (femfct_prox_trials' expression)
+ * with lambda_t = 0.0 exactly, and femfct_prox_trials' bits, where that trial's norm is <= budget, else lambda_t > 0 the
+ * root of ||c_out[t]||_{1,h} = budget: value by value the projection of the prox onto {box, ||.||_{1,h} <= budget} in the
+ * nodal inner product with the weights dt*w_l*ml_i.  src_out[t] = 1.0*g + 1.0*c_out[t] (g NULL: c_out[t]; src_out may be
+ * NULL).  d_dev NULL, with K = 1 only: x = c, tau = 0, the projection of c itself.  lambda_host[t], l1_host[t] =
+ * femfct_l1_norm_Q of the written trial bit for bit, rounds_host[t] = search rounds used (<= 16; one launch and one
+ * read-back of 19 K doubles each).  No atomics, fixed trees: two calls return the same bits.  budget not finite-positive,
+ * alpha < 0, a box without 0, K outside 1..FEMFCT_MAX_TRIALS, num_steps < 0, no mass matrix, or a NaN / Inf in c or d
+ * (found in the first read-back, before any search) is FEMFCT_ERR_INVALID.  Synchronises. */
+int femfct_budget_trials(femfct_ctx* ctx, const double* c_dev, const double* d_dev, const double* g_dev, double s0, int32_t K,
+                         double alpha, double budget, double c_lower, double c_upper, int32_t num_steps, double dt,
+                         double* c_out_dev, double* src_out_dev, double* lambda_host, double* l1_host, int32_t* rounds_host);
 
 /* Ensemble drift control (solvers.ensemble_solidbody; added after ABI version 5, backward compatible; an extension without
  * a counterpart in the reference): one control c serves S scenarios, 1 <= S <= FEMFCT_MAX_MEMBERS, each with its own state
